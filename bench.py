@@ -1,5 +1,17 @@
 """Benchmark: pixels/sec through estimate_disp + lrt (BASELINE.json metric).
 
+A plain run (--gpus / --steps / --warmup) does what the headline figure
+needs and no more: the untimed setup, the warm-up steps, the timed steps, and
+the result line (metric, value, unit, ms_per_step, the workload).
+--dump-outputs DIR also writes what the last timed step returned
+(disp_per_dist at the distances the inputs hold pixels at -- the others are
+NaN by contract --; p, llr, mu0, mu1, disp -- q where the step runs BH -- at
+a fixed seeded sample of pixels) as DIR/<name>.npy in float64; the inputs
+are seeded, so two builds can be compared output for output. Everything else
+described below -- the CPU baselines, the measured peaks and rooflines, the
+extra profiled step, result_sha16, the parity checks, the end-to-end legs,
+cfg3 / cfg4 beside the cfg2 line -- runs only with --full.
+
 Workloads (BASELINE.json configs):
 - cfg2 (configs[1], the N = 1 default): one synthetic chromosome of 20,000
   bins, 4 replicates (2 + 2 conditions), dist_thresh_max 250 (SURVEY.md §8(d)
@@ -861,6 +873,43 @@ def _outputs(torch, dev, n, C):
             'disp': torch.empty((n, C), dtype=torch.float64, device=dev)}
 
 
+# --dump-outputs: 7 or 8 float64 per sampled pixel and its index, 32 MB
+DUMP_PIXELS = 500000
+
+
+def distances_present(torch, dist, t_dist, D):
+    """Which of the D distances the workload's inputs hold a pixel at (over
+    all ranks): estimate_disp returns NaN at the others by contract. A
+    collective at N > 1 -- every rank calls it."""
+    cnt = torch.bincount(t_dist.long().clamp_(0, D), minlength=D + 1)[:D]
+    if dist:
+        dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+    return cnt.cpu().numpy() > 0
+
+
+def dump_outputs(path, torch, o, n, dpd, present, names):
+    """--dump-outputs: what the last timed step returned, as
+    ``path/<name>.npy`` (float64): disp_per_dist at the distances the inputs
+    hold pixels at (``present``, chosen from the inputs alone;
+    disp_per_dist_distances.npy lists them -- the other rows are NaN by
+    contract and are left out, a NaN at a present distance is kept), and the
+    per-pixel outputs ``names`` of ``o`` at sample_idx.npy -- every pixel up
+    to DUMP_PIXELS, else a fixed seeded sample of that many (sorted)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, 'disp_per_dist.npy'),
+            np.asarray(dpd, dtype=np.float64)[present])
+    np.save(os.path.join(path, 'disp_per_dist_distances.npy'),
+            np.flatnonzero(present).astype(np.float64))
+    idx = np.arange(n) if n <= DUMP_PIXELS else np.sort(
+        np.random.default_rng(0).choice(n, DUMP_PIXELS, replace=False))
+    np.save(os.path.join(path, 'sample_idx.npy'), idx.astype(np.float64))
+    t_idx = torch.from_numpy(idx).to(o['p'].device)
+    for k in names:
+        np.save(os.path.join(path, k + '.npy'),
+                o[k][t_idx].cpu().numpy().astype(np.float64, copy=False))
+
+
 def _upload(torch, dev, raw, f, dist_np):
     return (torch.from_numpy(np.ascontiguousarray(raw, dtype=np.int32)).to(dev),
             torch.from_numpy(np.ascontiguousarray(f)).to(dev),
@@ -920,11 +969,13 @@ def table_lrt(torch, dev, ctx, D, C):
     return run
 
 
-def timed_run(args, ctx, dist, dev, step):
+def timed_run(args, ctx, dist, dev, step, after_timed=None):
     """W untimed steps, then exactly K timed steps between barrier +
     synchronize on both sides (HIP events on the roofline kernels inside),
-    then one untimed step with every kernel scope timed. Returns
-    (elapsed max over ranks, roofline-kernel events, per-kernel ms)."""
+    then ``after_timed()`` (the last timed step's outputs are still in
+    place), then -- with --full -- one untimed step with every kernel scope
+    timed. Returns (elapsed max over ranks, roofline-kernel events,
+    per-kernel ms or None)."""
     import torch
     for _ in range(args.warmup):
         step()
@@ -943,14 +994,18 @@ def timed_run(args, ctx, dist, dev, step):
     elapsed = time.perf_counter() - t0
     ctx.profile(False)
     ev = {k: ctx.profile_read(k) for k in ('disp_work', 'lrt')}
-    ctx.profile_reset()
-    ctx.profile(True, level=2)
-    step()
-    torch.cuda.synchronize()
-    ctx.profile(False)
-    per = {k: ctx.profile_read(k) for k in
-           ('disp_reduce', 'disp_update', 'disp_nll', 'disp_prep', 'disp_work',
-            'lrt')}
+    if after_timed is not None:
+        after_timed()
+    per = None
+    if args.full:
+        ctx.profile_reset()
+        ctx.profile(True, level=2)
+        step()
+        torch.cuda.synchronize()
+        ctx.profile(False)
+        per = {k: ctx.profile_read(k) for k in
+               ('disp_reduce', 'disp_update', 'disp_nll', 'disp_prep',
+                'disp_work', 'lrt')}
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -969,6 +1024,20 @@ def total_over_ranks(dist, dev, n):
 
 def bench_line(args, world, n_local, tot_px, R, C, elapsed, ev, per, bins,
                dmax, workload, parallelism, scaling, peaks=None):
+    """The result line: the headline figure and its workload; with --full
+    (``per``: the profiled step's kernel times) the rooflines as well."""
+    line = {
+        'metric': METRIC, 'value': tot_px * args.steps / elapsed,
+        'unit': 'pixels/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+        'higher_is_better': True, 'scaling': scaling,
+        'vs_baseline': None, 'dtype': 'f64',
+        'data': 'synthetic (SURVEY.md 8(d) generator; no demo data '
+                'offline)',
+        'config': {'workload': workload, 'disp_pixels_rank0': n_local,
+                   'disp_pixels_total': tot_px, 'parallelism': parallelism}}
+    if per is None:
+        return line
     w_ms, w_n, w_bytes = ev['disp_work']
     l_ms, l_n, _ = ev['lrt']
     n_ms, n_n, n_bytes = per['disp_nll']
@@ -1037,16 +1106,7 @@ def bench_line(args, world, n_local, tot_px, R, C, elapsed, ev, per, bins,
                 'incomplete-gamma series / continued fractions'}
     kernels = {k: v[0] for k, v in per.items()}
     kernels['note'] = 'one extra untimed step, every kernel timed (rank 0)'
-    return {
-        'metric': METRIC, 'value': tot_px * args.steps / elapsed,
-        'unit': 'pixels/s', 'n_gpus': world, 'steps': args.steps,
-        'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
-        'higher_is_better': True, 'scaling': scaling,
-        'vs_baseline': None, 'dtype': 'f64',
-        'data': 'synthetic (SURVEY.md 8(d) generator; no demo data '
-                'offline)',
-        'config': {'workload': workload, 'disp_pixels_rank0': n_local,
-                   'disp_pixels_total': tot_px, 'parallelism': parallelism},
+    line.update({
         'roofline': roof,
         'kernel_rooflines': {
             'nll_brent': {
@@ -1074,7 +1134,8 @@ def bench_line(args, world, n_local, tot_px, R, C, elapsed, ev, per, bins,
             'equalize_pixel_reps': w_bytes / 20.0 / args.steps,
             'nll_pixel_reps': n_bytes / 8.0,
             'equalize_launches': w_n / args.steps},
-    }
+    })
+    return line
 
 
 OTHER_CONFIGS = {
@@ -1230,7 +1291,15 @@ def run_cfg2(args, world, rank, local, dist, ctx, dev, cpu, cfg3=None,
             last['dpd'] = dpd
             return dpd
 
-        elapsed, ev, per = timed_run(args, ctx, dist, dev, step)
+        def dump():
+            if not args.dump_outputs:
+                return
+            present = distances_present(torch, dist, t_dist, D)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, torch, o, n, last['dpd'],
+                             present, ('p', 'llr', 'mu0', 'mu1', 'disp'))
+
+        elapsed, ev, per = timed_run(args, ctx, dist, dev, step, dump)
         tot_px = total_over_ranks(dist, dev, n)
         if rank != 0:
             return None
@@ -1248,6 +1317,8 @@ def run_cfg2(args, world, rank, local, dist, ctx, dev, cpu, cfg3=None,
                 'Brent per rank, table all-reduce' if by_dist
                 else 'per-pass NLL all-reduce over RCCL'), 'weak',
             peaks=peaks)
+        if not args.full:
+            return out
         out['gang_aborts'] = ctx.profile_read('gang_aborts')[1]
         # the last step's disp_per_dist and p, hashed: A/B runs of kernel
         # variants that must not move a bit compare this
@@ -1374,6 +1445,7 @@ def run_cfg3(args, world, rank, local, dist, ctx, dev, peaks=None):
         or (world == 1 and args.noop_reduce)
     reduce = (parallel.make_allreduce() if world > 1 else
               (lambda ptr, count: None)) if per_pass else None
+    last = {}
 
     def step():
         if per_pass:
@@ -1403,9 +1475,21 @@ def run_cfg3(args, world, rank, local, dist, ctx, dev, peaks=None):
             o['q'] = parallel.bh_sharded(o['p'], bh_ops)
         else:
             ctx.bh_dev(o['p'].data_ptr(), n, o['q'].data_ptr())
+        last['dpd'] = dpd
         return dpd
 
-    elapsed, ev, per = timed_run(args, ctx, dist, dev, step)
+    def dump():
+        # (N > 1: rank 0's own pixels; q where BH leaves one per pixel)
+        if not args.dump_outputs:
+            return
+        present = distances_present(torch, dist, t_dist, D)
+        if rank == 0:
+            names = ('p', 'llr', 'mu0', 'mu1', 'disp') + \
+                (('q',) if len(o['q']) == n else ())
+            dump_outputs(args.dump_outputs, torch, o, n, last['dpd'], present,
+                         names)
+
+    elapsed, ev, per = timed_run(args, ctx, dist, dev, step, dump)
     tot_px = total_over_ranks(dist, dev, n)
     if rank != 0:
         return None
@@ -1430,7 +1514,8 @@ def run_cfg3(args, world, rank, local, dist, ctx, dev, peaks=None):
                                          'arrival' if compact else
                                          '52-byte raw / f / dist records')),
         'strong', peaks=peaks)
-    out['gang_aborts'] = ctx.profile_read('gang_aborts')[1]
+    if args.full:
+        out['gang_aborts'] = ctx.profile_read('gang_aborts')[1]
     out['config']['chromosomes_rank0'] = [int(i) for i in mine]
     out['config']['generate_s_rank0'] = gen_s
     if emu:
@@ -1449,6 +1534,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline figure: the CPU '
+                         'baselines, the measured peaks, the rooflines and '
+                         'the profiled step, the parity checks, the e2e legs '
+                         'and the other configs (each with its --no-* '
+                         'switch). Without it: set-up, warm-up, the timed '
+                         'steps, --dump-outputs, the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one '
+                         'returned to DIR/<name>.npy (float64; a fixed '
+                         'seeded sample of the per-pixel arrays)')
     ap.add_argument('--config', choices=('auto', 'cfg2', 'cfg3'),
                     default='auto',
                     help='auto: cfg2 (BASELINE configs[1], 1 GPU) at N = 1, '
@@ -1480,6 +1576,11 @@ def main():
                          'GPU with a no-op reduce, i.e. the N > 1 kernel and '
                          'host-sync path without the collective')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if not args.full:
+        args.no_cpu_baseline = args.no_e2e = args.no_peaks = True
+        args.no_other_configs = True
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))

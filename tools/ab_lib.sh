@@ -27,7 +27,7 @@ specs=${1:?"specs"}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 if [ "$cfg" = 2 ]; then
-  cmd="bench.py --no-cpu-baseline --no-e2e --no-other-configs --no-peaks --steps ${steps:-10}"
+  cmd="bench.py --full --no-cpu-baseline --no-e2e --no-other-configs --no-peaks --steps ${steps:-10}"
 else
   cmd="tools/run_cfg.py --cfg $cfg --steps ${steps:-2} --warmup 1"
 fi

@@ -4,7 +4,8 @@
 # recipes:
 #   final    rocprofv3 kernel stats + trace gaps of the default bench command
 #            (tools/gpu_prof_step.sh), its PMC passes (tools/pmc_passes.sh),
-#            then the full default bench line -> gpurun_out/<tag>_bench.json
+#            then the full default bench line (bench.py --full) ->
+#            $H3D_OUT/<tag>_bench.json (H3D_OUT: default records/)
 #            (r06f, r06g; tools/pmc_default.py <tag> profiles/r06/<x> then
 #            makes the summary the bench's default)
 #   suite    the -m gpu suite and smoke() (tools/gpu_suite.sh)
@@ -26,8 +27,10 @@ case $recipe in
   final)
     bash tools/gpu_prof_step.sh "$tag" > gpurun_out/${tag}_top.txt 2>&1 || exit 1
     bash tools/pmc_passes.sh "$tag" || exit 1
-    timeout -k 10 900 python3 -u bench.py > gpurun_out/${tag}_bench.json \
-      2> gpurun_out/${tag}_bench.err || exit 1
+    out=${H3D_OUT:-records}
+    mkdir -p "$out"
+    timeout -k 10 900 python3 -u bench.py --full > "$out/${tag}_bench.json" \
+      2> "$out/${tag}_bench.err" || exit 1
     head -12 gpurun_out/${tag}_top.txt ;;
   suite)
     bash tools/gpu_suite.sh "$tag" ;;
@@ -42,7 +45,7 @@ case $recipe in
     for rep in $(seq "$reps"); do
       for spec in $specs; do
         name=${spec%%:*}; envs=${spec#*:}
-        env $envs timeout -k 10 300 python3 -u bench.py --steps 1 --warmup 1 \
+        env $envs timeout -k 10 300 python3 -u bench.py --full --steps 1 --warmup 1 \
           --no-cpu-baseline --no-other-configs --no-cpu-cfg3 --no-peaks \
           > gpurun_out/${tag}_$name$rep.json 2> gpurun_out/${tag}_$name$rep.err || exit 1
         python3 -c "import json; d=json.loads(open('gpurun_out/${tag}_$name$rep.json').read().strip().splitlines()[-1]); f=lambda e: {k: (round(v*1e3,1) if isinstance(v,float) else v) for k,v in e.items() if k not in ('note','first_run','runs_total_s','gc_collections')}; print('$name', f(d['e2e_run_to_qvalues'])); print('$name', f(d['e2e_cfg3_run_to_qvalues']))"
