@@ -204,7 +204,9 @@ int work_grid(h3d_ctx* ctx, K kernel, size_t max_items) {
   return (int)std::max<size_t>(1, std::min<size_t>(max_items, (size_t)ctx->n_cu * nb));
 }
 
-template <int M, bool NLL>
+// (kFull: every condition has exactly M replicates -- k_disp_work's
+// replicate count is the constant M, see k_brent)
+template <int M, bool NLL, bool kFull = false>
 void launch_disp_work(h3d_ctx* ctx, size_t max_items, const int32_t* raw_s,
                       const double* f_s, double* pd, int64_t n,
                       const int64_t* cs, const int32_t* cl, const int32_t* cd,
@@ -217,7 +219,7 @@ void launch_disp_work(h3d_ctx* ctx, size_t max_items, const int32_t* raw_s,
     ProfScope ps(ctx, "disp_work", 0, 1);
 #define H3D_EQ(WW)                                                                  \
   do {                                                                              \
-    auto k = k_disp_work<M, WW, kEqualize, NLL>;                                    \
+    auto k = k_disp_work<M, WW, kEqualize, NLL, kFull>;                             \
     hipLaunchKernelGGL(k, dim3(work_grid(ctx, k, max_items)), dim3(kBlock), 0,      \
                        ctx->stream, raw_s, f_s, pd, n, cs, cl, cd, C, rep_idx, n_rep, \
                        st, seg_flags, list, meta, partial, ctx->eq_static8);        \
@@ -259,14 +261,15 @@ void launch_disp_work(h3d_ctx* ctx, size_t max_items, const int32_t* raw_s,
 }
 
 // the whole Brent search of every freshly equalized segment (single rank)
-template <int M>
+// (kFull: every condition has exactly M replicates, see k_brent)
+template <int M, bool kFull = false>
 void launch_brent(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t* seg_start,
                   int S, int C, const int32_t* rep_idx, const int32_t* n_rep,
                   SegState* st, const int* seg_flags, double* result, int* queue,
                   const int32_t* gate_meta = nullptr, int live_min = 0,
                   const int* gang_abort = nullptr, bool queue_zeroed = false) {
   ProfScope ps(ctx, "disp_nll", 0);
-  auto k = k_brent<M>;
+  auto k = k_brent<M, kFull>;
   constexpr int kBrentBlock = brent_block<M>();
   const size_t lds_max = M <= 8 ? (size_t)ctx->brent_lds_kb * 1024 : 0;
   int& nb = ctx->resident[(const void*)k];
@@ -284,7 +287,12 @@ void launch_brent(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t* seg_
   // CU's LDS (one 1024-thread workgroup per CU), minus the static part
   // (M >= 16: 512-thread workgroups, two per CU -- staging would halve that)
   const size_t lds_bytes = M <= 8 ? (size_t)ctx->brent_lds_kb * 1024 : 0;
-  const int64_t lds_px = (int64_t)(lds_bytes / (8 * (size_t)M));
+  // (whole blocks of pixels: thread t then adds pixels t, t + block, ... of
+  // the segment in that order wherever the head ends, so the sum's bits do
+  // not depend on H3D_BRENT_LDS_KB; the default and every measured size
+  // already were -- 16 KB at M = 4, 512 pixels, gave other last bits)
+  const int64_t lds_px =
+      (int64_t)(lds_bytes / (8 * (size_t)M)) / kBrentBlock * kBrentBlock;
   if (!queue_zeroed) (void)hipMemsetAsync(queue, 0, sizeof(int), ctx->stream);
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBrentBlock), lds_px ? lds_px * 8 * M : 0,
                      ctx->stream, pd, n, seg_start, S, C, rep_idx, n_rep, st, seg_flags,
@@ -452,7 +460,7 @@ int gang_setup_dev(h3d_ctx* ctx, int64_t n, int D, int C, GangTables* g) {
   return 0;
 }
 
-template <int M>
+template <int M, bool kFull = false>
 void launch_brent_gang(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t* seg_start,
                        int S, int C, const int32_t* rep_idx, const int32_t* n_rep,
                        SegState* st, const int* seg_flags, double* result, int* queue,
@@ -462,7 +470,20 @@ void launch_brent_gang(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t*
   if (!queue_zeroed) (void)hipMemsetAsync(queue, 0, sizeof(int), ctx->stream);
   const int epoch = gang_next_epoch(ctx, g, S);
   const int grid = std::max(1, std::min(g.T, g.grid));
-  hipLaunchKernelGGL(k_brent_gang<M>, dim3(grid), dim3(kGangThreads), 0, ctx->stream, pd,
+  auto k = k_brent_gang<M, kFull>;
+  if constexpr (kFull) {
+    // the slices and the resident grid were sized for k_brent_gang<M>
+    // (gang_setup*; the slice size decides the sum's association, so it is
+    // the same for both instantiations): the kFull one runs only where as
+    // many of its workgroups are resident
+    int& nb = ctx->resident[(const void*)k];
+    if (nb == 0 &&
+        (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kGangThreads, 0) != hipSuccess ||
+         nb < 1))
+      nb = 1;
+    if (ctx->n_cu * nb < g.grid) k = k_brent_gang<M, false>;
+  }
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kGangThreads), 0, ctx->stream, pd,
                      n, seg_start, S, C, rep_idx, n_rep, st, seg_flags, result, queue,
                      g.task_seg, g.task_g, g.T, g.P, g.part, g.tag, g.gmax, g.abort,
                      g.timeout, ctx->work_count, epoch, gate_meta, live_max);
@@ -537,6 +558,7 @@ h3d_ctx* h3d_open(int device) {
   if (const char* e = std::getenv("H3D_DISP_M2")) ctx->disp_m2 = std::atoi(e);
   if (const char* e = std::getenv("H3D_BRENT")) ctx->brent_gang = std::atoi(e);
   if (const char* e = std::getenv("H3D_BRENT_LDS_KB")) ctx->brent_lds_kb = std::atoi(e);
+  if (const char* e = std::getenv("H3D_NLL_FULL")) ctx->nll_full = std::atoi(e);
   if (const char* e = std::getenv("H3D_GANG_P")) ctx->gang_px = std::atoi(e);
   if (const char* e = std::getenv("H3D_DEV_SEG_TABLES")) ctx->dev_seg_tables = std::atoi(e);
   if (hipMalloc((void**)&ctx->work_count, 2 * sizeof(unsigned long long)) != hipSuccess ||
@@ -1021,6 +1043,12 @@ int disp_per_dist_core(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
                     : maxnr <= 8                  ? 8
                     : maxnr <= 16                 ? 16
                                                   : 32;
+  // every condition has exactly mslot replicates: the kFull instantiations
+  // of the equalize pass and the Brent kernels (M = 2 only, see k_brent;
+  // H3D_NLL_FULL=0: never)
+  const bool nll_full =
+      ctx->nll_full && mslot == 2 &&
+      std::all_of(nrep.begin(), nrep.end(), [&](int r) { return r == mslot; });
   // dev_tables, single rank: k_brent and k_brent_gang are both launched every
   // qcml iteration and the DEVICE picks one by the live-segment count (one
   // workgroup per segment while they fill the CUs, gangs for the tail
@@ -1102,29 +1130,31 @@ int disp_per_dist_core(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
     batch = 5;
     while (true) {
       for (int b = 0; b < batch; ++b) {
-#define H3D_QCML_ITER(MM)                                                                 \
-  launch_disp_work<MM, false>(ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C,     \
-                              d_repidx, d_nrep, d_st, d_flags, d_list, d_meta, d_partial); \
+#define H3D_QCML_ITER(MM, FF)                                                             \
+  launch_disp_work<MM, false, FF>(                                                        \
+      ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st,     \
+      d_flags, d_list, d_meta, d_partial);                                                \
   dbg_launch("equalize");                                                                 \
   if (dual_on) {                                                                          \
-    launch_brent<MM>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res,      \
-                     d_queue, d_meta, ctx->n_cu, gang.abort, true);                        \
+    launch_brent<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res,  \
+                         d_queue, d_meta, ctx->n_cu, gang.abort, true);                    \
     dbg_launch("k_brent (dual)");                                                         \
-    launch_brent_gang<MM>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res, \
-                          d_queue + 1, gang, d_meta, ctx->n_cu, true);                    \
+    launch_brent_gang<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags,    \
+                              d_res, d_queue + 1, gang, d_meta, ctx->n_cu, true);         \
     dbg_launch("k_brent_gang (dual)");                                                    \
   } else if (use_gang)                                                                    \
-    launch_brent_gang<MM>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res, \
-                          d_queue + 1, gang, nullptr, 0, true);                           \
+    launch_brent_gang<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags,    \
+                              d_res, d_queue + 1, gang, nullptr, 0, true);                \
   else                                                                                    \
-    launch_brent<MM>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res,      \
-                     d_queue, nullptr, 0, nullptr, true)
+    launch_brent<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res,  \
+                         d_queue, nullptr, 0, nullptr, true)
         dbg_launch("before qcml iteration");
-        if (mslot == 2) { H3D_QCML_ITER(2); }
-        else if (mslot == 4) { H3D_QCML_ITER(4); }
-        else if (mslot == 8) { H3D_QCML_ITER(8); }
-        else if (mslot == 16) { H3D_QCML_ITER(16); }
-        else { H3D_QCML_ITER(32); }
+        if (mslot == 2 && nll_full) { H3D_QCML_ITER(2, true); }
+        else if (mslot == 2) { H3D_QCML_ITER(2, false); }
+        else if (mslot == 4) { H3D_QCML_ITER(4, false); }
+        else if (mslot == 8) { H3D_QCML_ITER(8, false); }
+        else if (mslot == 16) { H3D_QCML_ITER(16, false); }
+        else { H3D_QCML_ITER(32, false); }
 #undef H3D_QCML_ITER
         {
           ProfScope ps(ctx, "disp_update", 0);

@@ -140,6 +140,11 @@ struct h3d_ctx {
   // LDS too, r03am: 64 / 96 / 128 KB 2.62-2.66 ms of Brent per cfg2 step,
   // 80 / 112 / 144 KB 2.73-2.80 (the replicate rows' LDS stride), 0 KB 2.67
   int brent_lds_kb = 128;
+  // H3D_NLL_FULL: a call whose conditions all have exactly two replicates
+  // (M = 2) runs the kFull instantiations of the equalize pass and the Brent
+  // kernels (the replicate count a constant, predicate-free Brent trips; the
+  // same bits); 0 = always the general ones
+  int nll_full = 1;
   double qcml_tol = 1e-4;  // h3d_set_qcml_tol (qcml's tol, dispersion.py:10)
   // gang Brent slice (pixels; 0 = sized from the call, gang_setup_dev)
   int gang_px = 0;

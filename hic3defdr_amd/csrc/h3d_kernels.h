@@ -431,7 +431,13 @@ static __global__ __launch_bounds__(1024) void k_disp_tables(
 constexpr int kTaskHeadStride = 32;
 constexpr int kWorkMetaInts = kTaskHeadStride * 17;
 
-template <int M, int W, int PH, bool NLL = true>
+// kFull (the single-rank equalize pass of a call whose conditions all have
+// exactly M = 2 replicates, H3D_NLL_FULL): the replicate count is the
+// constant M, which folds the `k < nr` selects on x, f and lf, np_sum's and
+// fit_mu's replicate tests. The same bits. 128 VGPRs and 16 B of scratch at 4
+// waves (the general instantiation 32 B); measured on cfg2, equalize 2.55-2.57
+// -> 2.43-2.45 ms per step (profiles/r07).
+template <int M, int W, int PH, bool NLL = true, bool kFull = false>
 __global__ __launch_bounds__(kBlock, W) void k_disp_work(
     const int32_t* __restrict__ raw_s, const double* __restrict__ f_s,
     double* __restrict__ pd, int64_t n, const int64_t* __restrict__ chunk_start,
@@ -499,7 +505,7 @@ __global__ __launch_bounds__(kBlock, W) void k_disp_work(
     const int chunk = item / C, c = item - chunk * C;
     const int s = chunk_d[chunk] * C + c;
     constexpr int phase = PH;
-    const int nr = n_rep[c];
+    const int nr = kFull ? M : n_rep[c];
     double term = 0.0;
     const int i = q * 64 + lane;
     H3D_SEC_BEGIN(t_task);
@@ -967,6 +973,163 @@ __device__ __forceinline__ double brent_segment_sum(
   return acc;
 }
 
+// brent_prio's levels without its per-trip quotient: the three trips at which
+// the level drops (the smallest trip with H3D_BRENT_PRIO_DIV * trip / ntr >=
+// 1, 2, 3) are found once per evaluation, a trip compares its index with the
+// next of them. Everything here is wave-uniform: the index counts the trips
+// of the wave's first lane, as brent_prio's readfirstlane did.
+template <bool kPrio>
+struct BrentProgress {
+  int b1 = 0, b2 = 0, b3 = 0;
+  __device__ __forceinline__ explicit BrentProgress(int ntr) {
+    if constexpr (kPrio) {
+      const int m = max(ntr, 1), dv = H3D_BRENT_PRIO_DIV;
+      b1 = __builtin_amdgcn_readfirstlane((m + dv - 1) / dv);
+      b2 = __builtin_amdgcn_readfirstlane((2 * m + dv - 1) / dv);
+      b3 = __builtin_amdgcn_readfirstlane((3 * m + dv - 1) / dv);
+      __builtin_amdgcn_s_setprio(3);
+    }
+  }
+  // the next trip at which the level drops, `last` the latest trip run
+  __device__ __forceinline__ int next_after(int last) const {
+    if constexpr (kPrio) return last >= b3 ? INT_MAX : last >= b2 ? b3 : last >= b1 ? b2 : b1;
+    else return 0;
+  }
+  // before trip t; `next` = next_after(t - 1), updated
+  __device__ __forceinline__ void enter(int t, int& next) const {
+    if constexpr (kPrio) {
+      if (t >= next) {
+        if (t >= b3) {
+          __builtin_amdgcn_s_setprio(0);
+          next = INT_MAX;
+        } else if (t >= b2) {
+          __builtin_amdgcn_s_setprio(1);
+          next = b3;
+        } else {
+          __builtin_amdgcn_s_setprio(2);
+          next = b2;
+        }
+      }
+    }
+  }
+  // the first lane's value of a per-lane count or flag
+  __device__ __forceinline__ static int first_lane(int v) {
+    if constexpr (kPrio) return __builtin_amdgcn_readfirstlane(v);
+    else return 0;
+  }
+};
+
+// brent_segment_sum for a condition with exactly M replicates (the kernels'
+// kFull instantiations): the same terms added in the same order, without the
+// instructions that only served predicates --
+// - the replicate count is M: no `k < nr` select on a load, np_sum and the
+//   lgamma fills unpredicated (nll_pixel* with n = M folds them);
+// - each loop is split into a thread's full trips (every pixel of the trip
+//   inside the range: no test, no select) and at most one remainder trip in
+//   brent_segment_sum's form;
+// - the priority level by BrentProgress;
+// - the tail's addresses: each replicate's row offset ri[k] * n + el is made
+//   wave-uniform once per evaluation and advanced by the trip's stride on the
+//   scalar unit; a lane adds its constant 32-bit byte offset.
+template <int M, int kBlockT, int MODE, bool kPrio = false>
+__device__ __forceinline__ double brent_segment_sum_full(
+    const double* s_pd, int64_t lds_px, const double* __restrict__ pd, int64_t n,
+    const int* ri, int64_t b, int64_t el, int64_t e, const NllConst& kc,
+    const LogTab* s_tab) {
+  constexpr int kPair = kPair2<M>();
+  constexpr int kStep = kPair * kBlockT;
+  double acc = 0.0;
+  const BrentProgress<kPrio> pg((int)((e - b + kStep - 1) / kStep));
+  [[maybe_unused]] int done = 0;  // trips of the wave's first lane so far
+  auto term = [&](const double* v) {
+    if constexpr (MODE == 2) return nll_pixel_large<M>(v, M, kc, s_tab);
+    else if constexpr (MODE == 1) return nll_pixel_mid<M>(v, M, kc, s_tab);
+    else return nll_pixel<M>(v, M, kc, s_tab);
+  };
+  // a thread's full trips over `len` pixels, its first at threadIdx.x
+  auto full_trips = [](int64_t len) {
+    const int64_t a = len - (int64_t)(kPair - 1) * kBlockT - (int64_t)threadIdx.x;
+    return a > 0 ? (int)((a + kStep - 1) / kStep) : 0;
+  };
+  // one trip: pixel q of it is ld(q, k), k the replicate; `left` (remainder
+  // trips) counts the range's pixels from the thread's first of the trip on
+  auto one_trip = [&](auto full, auto&& ld, int64_t left) {
+    constexpr bool kAll = decltype(full)::value;
+    double v[kPair][M];
+    bool on[kPair];
+#pragma unroll
+    for (int q = 0; q < kPair; ++q) {
+      on[q] = kAll || q == 0 || (int64_t)q * kBlockT < left;
+#pragma unroll
+      for (int k = 0; k < M; ++k) v[q][k] = on[q] ? ld(q, k) : 0.0;
+    }
+    double t[kPair];
+#pragma unroll
+    for (int q = 0; q < kPair; ++q) t[q] = term(v[q]);
+#pragma unroll
+    for (int q = 0; q < kPair; ++q)
+      if (on[q]) acc += t[q];
+  };
+  const int64_t hl = el - b;
+  if (hl > 0) {
+    const double* h[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) h[k] = s_pd + k * lds_px + threadIdx.x;
+    auto ld = [&](int q, int k) { return h[k][q * kBlockT]; };
+    const int nf = full_trips(hl);
+    int next = pg.next_after(done - 1);
+    for (int t = 0; t < nf; ++t) {
+      pg.enter(done + t, next);
+      one_trip(std::true_type(), ld, 0);
+#pragma unroll
+      for (int k = 0; k < M; ++k) h[k] += kStep;
+    }
+    done += pg.first_lane(nf);
+    const int64_t left = hl - ((int64_t)threadIdx.x + (int64_t)nf * kStep);
+    // a remainder trip is a trip of its own where the wave's first lane runs
+    // one; otherwise its lanes finish the trip the first lane ran as a full
+    // one, at the level set then
+    if (pg.first_lane(left > 0)) {
+      next = pg.next_after(done - 1);
+      pg.enter(done++, next);
+    }
+    if (left > 0) one_trip(std::false_type(), ld, left);
+  }
+  const int64_t tl = e - el;
+  if (tl > 0) {
+    int64_t row[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const uint64_t o = (uint64_t)((int64_t)ri[k] * n + el);
+      const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)o);
+      const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(o >> 32));
+      row[k] = (int64_t)(((uint64_t)hi << 32) | lo);
+    }
+    const uint32_t lane_off = threadIdx.x * 8u;
+    int64_t adv = 0;  // pixels before the trip: uniform in the loop
+    auto ld = [&](int q, int k) {
+      const char* p = (const char*)(pd + (row[k] + adv + q * kBlockT));
+      return *(const double*)(p + lane_off);
+    };
+    const int nf = full_trips(tl);
+    int next = pg.next_after(done - 1);
+    for (int t = 0; t < nf; ++t) {
+      pg.enter(done + t, next);
+      one_trip(std::true_type(), ld, 0);
+      adv += kStep;
+    }
+    done += pg.first_lane(nf);
+    adv = (int64_t)nf * kStep;  // the thread's own
+    const int64_t left = tl - ((int64_t)threadIdx.x + adv);
+    if (pg.first_lane(left > 0)) {
+      next = pg.next_after(done - 1);
+      pg.enter(done++, next);
+    }
+    if (left > 0) one_trip(std::false_type(), ld, left);
+  }
+  return acc;
+}
+
 // The segment's first `lds_px` pixels are staged in LDS once per search (the
 // dynamic shared buffer, up to ~150 KB: one 1024-thread workgroup per CU);
 // every evaluation reads them from there and streams only the rest -- the
@@ -984,7 +1147,15 @@ __device__ unsigned long long g_brent_clk[6 + 2 * 16];
 #define H3D_BADD(i, d)
 #endif
 
-template <int M>
+// kFull (here and in k_brent_gang): every condition of the call has exactly
+// M replicates -- the replicate count is the constant M and the sums run
+// brent_segment_sum_full. The same bits as the general instantiation.
+// Launched for M = 2 only: at M = 4 the full form spilled at the 128-VGPR
+// budget (k_brent<4, true> 304 B of scratch where k_brent<4> has none,
+// k_brent_gang<4, true> 205 VGPRs against 119), also with only the constant
+// count in brent_segment_sum's own loops (352 B, 192 VGPRs).
+
+template <int M, bool kFull = false>
 __global__ __launch_bounds__(brent_block<M>(), M >= 16 ? 2 : 4) void k_brent(
     const double* __restrict__ pd, int64_t n,
     const int64_t* __restrict__ seg_start /* D + 1 */, int S, int C,
@@ -1029,7 +1200,7 @@ __global__ __launch_bounds__(brent_block<M>(), M >= 16 ? 2 : 4) void k_brent(
       s_st.flags |= seg_flags[s];
     }
     const int d = s / C, c = s - (s / C) * C;
-    const int nr = n_rep[c];
+    const int nr = kFull ? M : n_rep[c];
     const int64_t b = seg_start[d], e = seg_start[d + 1];
     int ri[M];
 #pragma unroll
@@ -1051,11 +1222,20 @@ __global__ __launch_bounds__(brent_block<M>(), M >= 16 ? 2 : 4) void k_brent(
       // paths (nll_pixel_large / _mid), the same for every thread of the
       // segment
       constexpr bool kPr = H3D_BRENT_PRIO != 0;
-      const double acc = (kc.r >= kNllLargeR)
-          ? brent_segment_sum<M, kBrentBlock, 2, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab)
-          : (kc.r >= kNllMidR)
-          ? brent_segment_sum<M, kBrentBlock, 1, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab)
-          : brent_segment_sum<M, kBrentBlock, 0, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab);
+      double acc;
+      if constexpr (kFull) {
+        acc = (kc.r >= kNllLargeR)
+            ? brent_segment_sum_full<M, kBrentBlock, 2, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab)
+            : (kc.r >= kNllMidR)
+            ? brent_segment_sum_full<M, kBrentBlock, 1, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab)
+            : brent_segment_sum_full<M, kBrentBlock, 0, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab);
+      } else {
+        acc = (kc.r >= kNllLargeR)
+            ? brent_segment_sum<M, kBrentBlock, 2, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab)
+            : (kc.r >= kNllMidR)
+            ? brent_segment_sum<M, kBrentBlock, 1, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab)
+            : brent_segment_sum<M, kBrentBlock, 0, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab);
+      }
       double wacc = acc;
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) wacc += __shfl_xor(wacc, off, 64);
@@ -1155,8 +1335,12 @@ __global__ __launch_bounds__(brent_block<M>(), M >= 16 ? 2 : 4) void k_brent(
 // k_brent, which the host switches to once it sees the flag.
 constexpr int kGangThreads = 256;
 
-template <int M>
-__global__ __launch_bounds__(kGangThreads) void k_brent_gang(
+// (brent_segment_sum_full's trips took 141 VGPRs here, three waves per SIMD
+// where k_brent_gang<2> has four: the register budget of four keeps as many
+// of its workgroups resident as the gang tables were sized for; a second
+// argument of 0 sets no budget, as before)
+template <int M, bool kFull = false>
+__global__ __launch_bounds__(kGangThreads, (kFull ? 4 : 0)) void k_brent_gang(
     const double* __restrict__ pd, int64_t n,
     const int64_t* __restrict__ seg_start /* D + 1 */, int S, int C,
     const int32_t* __restrict__ rep_idx /* C x kMaxReps */,
@@ -1196,7 +1380,7 @@ __global__ __launch_bounds__(kGangThreads) void k_brent_gang(
       s_abort = 0;
     }
     const int d = s / C, c = s - (s / C) * C;
-    const int nr = n_rep[c];
+    const int nr = kFull ? M : n_rep[c];
     const int64_t b = seg_start[d], e = seg_start[d + 1];
     const int G = (int)((e - b + P - 1) / P);
     const int64_t sb = b + (int64_t)g * P;
@@ -1210,11 +1394,20 @@ __global__ __launch_bounds__(kGangThreads) void k_brent_gang(
       const NllConst kc = s_st.k;
       // the slice (no LDS head), two pixels per trip for M <= 4, as k_brent
       // (the progress priority of k_brent measured neutral here, r06z)
-      double acc = (kc.r >= kNllLargeR)
-          ? brent_segment_sum<M, kGangThreads, 2>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab)
-          : (kc.r >= kNllMidR)
-          ? brent_segment_sum<M, kGangThreads, 1>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab)
-          : brent_segment_sum<M, kGangThreads, 0>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab);
+      double acc;
+      if constexpr (kFull) {
+        acc = (kc.r >= kNllLargeR)
+            ? brent_segment_sum_full<M, kGangThreads, 2>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab)
+            : (kc.r >= kNllMidR)
+            ? brent_segment_sum_full<M, kGangThreads, 1>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab)
+            : brent_segment_sum_full<M, kGangThreads, 0>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab);
+      } else {
+        acc = (kc.r >= kNllLargeR)
+            ? brent_segment_sum<M, kGangThreads, 2>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab)
+            : (kc.r >= kNllMidR)
+            ? brent_segment_sum<M, kGangThreads, 1>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab)
+            : brent_segment_sum<M, kGangThreads, 0>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab);
+      }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
       if (lane == 0) wpart[wid] = acc;
