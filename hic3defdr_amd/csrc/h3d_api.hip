@@ -14,6 +14,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "h3d.h"
@@ -184,13 +185,15 @@ struct HostStamps {
   }
 };
 
-// workgroups of `kernel` that fit on one CU at once (queried once per kernel;
-// every device of a process is a gfx950)
+// workgroups of `kernel` (`block` threads, `dyn_lds` bytes of dynamic LDS)
+// that fit on one CU at once, queried once per kernel (every device of a
+// process is a gfx950)
 template <typename K>
-int resident_blocks(K kernel) {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, kBlock, 0) != hipSuccess ||
-      nb < 1)
+int resident_blocks(h3d_ctx* ctx, K kernel, int block, size_t dyn_lds = 0) {
+  int& nb = ctx->resident[(const void*)kernel];
+  if (nb == 0 &&
+      (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, dyn_lds) != hipSuccess ||
+       nb < 1))
     nb = 1;
   return nb;
 }
@@ -199,65 +202,23 @@ int resident_blocks(K kernel) {
 // the work list), at most one workgroup per item
 template <typename K>
 int work_grid(h3d_ctx* ctx, K kernel, size_t max_items) {
-  int& nb = ctx->resident[(const void*)kernel];
-  if (nb == 0) nb = resident_blocks(kernel);
-  return (int)std::max<size_t>(1, std::min<size_t>(max_items, (size_t)ctx->n_cu * nb));
+  const size_t wave = (size_t)ctx->n_cu * resident_blocks(ctx, kernel, kBlock);
+  return (int)std::max<size_t>(1, std::min<size_t>(max_items, wave));
 }
 
-// (kFull: every condition has exactly M replicates -- k_disp_work's
-// replicate count is the constant M, see k_brent)
-template <int M, bool NLL, bool kFull = false>
-void launch_disp_work(h3d_ctx* ctx, size_t max_items, const int32_t* raw_s,
-                      const double* f_s, double* pd, int64_t n,
-                      const int64_t* cs, const int32_t* cl, const int32_t* cd,
-                      int C, const int32_t* rep_idx, const int32_t* n_rep,
-                      const SegState* st, int* seg_flags, const int32_t* list,
-                      int32_t* meta, double* partial) {
-  // equalize pass (heavy: q2qnbinom), then (multi-rank driver) the NLL-only
-  // pass (light)
-  {
-    ProfScope ps(ctx, "disp_work", 0, 1);
-#define H3D_EQ(WW)                                                                  \
-  do {                                                                              \
-    auto k = k_disp_work<M, WW, kEqualize, NLL, kFull>;                             \
-    hipLaunchKernelGGL(k, dim3(work_grid(ctx, k, max_items)), dim3(kBlock), 0,      \
-                       ctx->stream, raw_s, f_s, pd, n, cs, cl, cd, C, rep_idx, n_rep, \
-                       st, seg_flags, list, meta, partial, ctx->eq_static8);        \
-  } while (0)
-    if constexpr (M == 2 && NLL) {
-      H3D_EQ(4);
-    } else if constexpr (M == 2) {
-      // H3D_DISP_W2: the R_c <= 2 path (cfg2's 2 + 2 design)
-      if (ctx->disp_w2 == 8) H3D_EQ(8);
-      else if (ctx->disp_w2 == 6) H3D_EQ(6);
-      else if (ctx->disp_w2 == 5) H3D_EQ(5);
-      else H3D_EQ(4);
-    } else if constexpr (M == 4) {
-      if (ctx->disp_w == 4) H3D_EQ(4);
-      else if (ctx->disp_w == 3) H3D_EQ(3);
-      else if (ctx->disp_w == 2) H3D_EQ(2);
-      else H3D_EQ(1);
-    } else if constexpr (M == 8) {
-      // H3D_DISP_W8: register budget of the M = 8 path (R_c <= 8, cfg4;
-      // W 1/2/3/4 measured 214/214/199/197 ms per cfg4 step, r02)
-      if (ctx->disp_w8 == 4) H3D_EQ(4);
-      else H3D_EQ(1);
-    } else {
-      H3D_EQ(1);
-    }
-#undef H3D_EQ
-  }
-  if constexpr (NLL) {
-    ProfScope ps(ctx, "disp_nll", 0);
-    auto k = k_disp_work<M, 1, kNll>;
-    if constexpr (M == 4) {
-      if (ctx->nll_w == 2) k = k_disp_work<M, 2, kNll>;
-      else if (ctx->nll_w == 4) k = k_disp_work<M, 4, kNll>;
-    }
-    hipLaunchKernelGGL(k, dim3(work_grid(ctx, k, max_items)), dim3(kBlock), 0,
-                       ctx->stream, raw_s, f_s, pd, n, cs, cl, cd, C, rep_idx, n_rep,
-                       st, seg_flags, list, meta, partial, ctx->eq_static8);
-  }
+// The kernels' replicate slot width M -- the smallest of 2, 4, 8, 16, 32 that
+// holds the largest condition -- and their kFull forms (M = 2 only, see
+// k_brent) are template arguments: fn(integral_constant<int, M>,
+// bool_constant<kFull>) runs with the call's pair.
+template <typename F>
+auto with_width(int mslot, bool nll_full, F&& fn) {
+  using std::integral_constant;
+  if (mslot == 2 && nll_full) return fn(integral_constant<int, 2>{}, std::true_type{});
+  if (mslot == 2) return fn(integral_constant<int, 2>{}, std::false_type{});
+  if (mslot == 4) return fn(integral_constant<int, 4>{}, std::false_type{});
+  if (mslot == 8) return fn(integral_constant<int, 8>{}, std::false_type{});
+  if (mslot == 16) return fn(integral_constant<int, 16>{}, std::false_type{});
+  return fn(integral_constant<int, 32>{}, std::false_type{});
 }
 
 // the whole Brent search of every freshly equalized segment (single rank)
@@ -271,22 +232,15 @@ void launch_brent(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t* seg_
   ProfScope ps(ctx, "disp_nll", 0);
   auto k = k_brent<M, kFull>;
   constexpr int kBrentBlock = brent_block<M>();
-  const size_t lds_max = M <= 8 ? (size_t)ctx->brent_lds_kb * 1024 : 0;
-  int& nb = ctx->resident[(const void*)k];
-  if (nb == 0) {
-    if (lds_max)
-      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_max);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kBrentBlock, lds_max) !=
-            hipSuccess ||
-        nb < 1)
-      nb = 1;
-  }
-  const int grid = std::max(1, std::min(S, ctx->n_cu * nb));
   // LDS staging of each segment's head: the workgroup's whole share of the
   // CU's LDS (one 1024-thread workgroup per CU), minus the static part
   // (M >= 16: 512-thread workgroups, two per CU -- staging would halve that)
   const size_t lds_bytes = M <= 8 ? (size_t)ctx->brent_lds_kb * 1024 : 0;
+  if (lds_bytes && !ctx->resident.count((const void*)k))
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+  const int grid =
+      std::max(1, std::min(S, ctx->n_cu * resident_blocks(ctx, k, kBrentBlock, lds_bytes)));
   // (whole blocks of pixels: thread t then adds pixels t, t + block, ... of
   // the segment in that order wherever the head ends, so the sum's bits do
   // not depend on H3D_BRENT_LDS_KB; the default and every measured size
@@ -355,30 +309,14 @@ long long gang_timeout(h3d_ctx* ctx) {
   return (long long)khz * 500;
 }
 
-// Returns 1 (nothing set up) when one workgroup per segment already fills
-// the chip -- the gang's exchange only pays where CUs would idle -- or when
-// a gang would not fit the resident grid.
+// The host-built gang tables (H3D_BRENT=2: every search in gangs). Returns 1
+// (nothing set up) when a gang would not fit the resident grid.
 template <int M>
 int gang_setup(h3d_ctx* ctx, const std::vector<int64_t>& seg_start, int D, int C,
                GangTables* g) {
-  auto k = k_brent_gang<M>;
-  int& nb = ctx->resident[(const void*)k];
-  if (nb == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kGangThreads, 0) != hipSuccess ||
-        nb < 1)
-      nb = 1;
-  }
-  g->grid = ctx->n_cu * nb;
-  int live = 0;
+  g->grid = ctx->n_cu * resident_blocks(ctx, k_brent_gang<M>, kGangThreads);
   int64_t total = 0;
-  for (int d = 0; d < D; ++d) {
-    const int64_t np = seg_start[d + 1] - seg_start[d];
-    if (np) live += C;
-    total += np * C;
-  }
-  // H3D_BRENT=1 (auto): gangs when the segments leave CUs without a
-  // workgroup; 2: always
-  if (ctx->brent_gang == 1 && live >= ctx->n_cu) return 1;
+  for (int d = 0; d < D; ++d) total += (seg_start[d + 1] - seg_start[d]) * C;
   // slices: about two resident grids of them over the whole call, at least
   // 1024 pixels (4 per thread)
   int64_t P = (total + 2 * (int64_t)g->grid - 1) / (2 * (int64_t)g->grid);
@@ -429,14 +367,7 @@ int gang_setup(h3d_ctx* ctx, const std::vector<int64_t>& seg_start, int D, int C
 // possible segment (all n pixels).
 template <int M>
 int gang_setup_dev(h3d_ctx* ctx, int64_t n, int D, int C, GangTables* g) {
-  auto k = k_brent_gang<M>;
-  int& nb = ctx->resident[(const void*)k];
-  if (nb == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kGangThreads, 0) != hipSuccess ||
-        nb < 1)
-      nb = 1;
-  }
-  g->grid = ctx->n_cu * nb;
+  g->grid = ctx->n_cu * resident_blocks(ctx, k_brent_gang<M>, kGangThreads);
   const int64_t total = n * C;
   int64_t P = (total + 2 * (int64_t)g->grid - 1) / (2 * (int64_t)g->grid);
   P = std::max<int64_t>(P, (n + g->grid - 1) / g->grid);
@@ -476,12 +407,7 @@ void launch_brent_gang(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t*
     // (gang_setup*; the slice size decides the sum's association, so it is
     // the same for both instantiations): the kFull one runs only where as
     // many of its workgroups are resident
-    int& nb = ctx->resident[(const void*)k];
-    if (nb == 0 &&
-        (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kGangThreads, 0) != hipSuccess ||
-         nb < 1))
-      nb = 1;
-    if (ctx->n_cu * nb < g.grid) k = k_brent_gang<M, false>;
+    if (ctx->n_cu * resident_blocks(ctx, k, kGangThreads) < g.grid) k = k_brent_gang<M, false>;
   }
   hipLaunchKernelGGL(k, dim3(grid), dim3(kGangThreads), 0, ctx->stream, pd,
                      n, seg_start, S, C, rep_idx, n_rep, st, seg_flags, result, queue,
@@ -498,6 +424,679 @@ int64_t disp_work_bytes(h3d_ctx* ctx, bool nll) {
   (void)hipMemcpyAsync(c, ctx->work_count, sizeof(c), hipMemcpyDeviceToHost, ctx->stream);
   (void)hipStreamSynchronize(ctx->stream);
   return nll ? (int64_t)(c[1] * 8ull) : (int64_t)(c[0] * 20ull);
+}
+
+// ---------------------------------------------------------------------------
+// estimate_disp: the driver. disp_per_dist_core reads as its stages; what
+// they share travels in a DispCall.
+// ---------------------------------------------------------------------------
+
+// H3D_DEBUG: the first launch error of the estimate_disp driver, by site
+void dbg_launch(const char* where) {
+  static const bool on = std::getenv("H3D_DEBUG") != nullptr;
+  if (!on) return;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) fprintf(stderr, "[h3d] launch error at %s: %s\n", where, hipGetErrorString(e));
+}
+
+// h3d_estimate_disp_dev's request: the smoothed tables of the result, on the
+// device, enqueued behind the result copies
+struct TableReq {
+  int weighted;
+  double frac, aff;
+  double* d_tables;
+};
+
+struct DispCall {
+  h3d_ctx* ctx = nullptr;
+  hipStream_t s = nullptr;
+  // the request
+  const int32_t* d_raw = nullptr;
+  const double* d_f = nullptr;
+  const int32_t* d_dist = nullptr;
+  int64_t n = 0;
+  int R = 0, C = 0, D = 0;
+  h3d_allreduce_fn reduce = nullptr;
+  void* user = nullptr;
+  const TableReq* treq = nullptr;
+  // the plan: S segments, the kernels' replicate slot width and whether
+  // every condition fills it (with_width)
+  int S = 0, mslot = 0;
+  bool nll_full = false;
+  std::vector<int> nrep;
+  std::vector<int32_t> rep_idx;
+  // The per-call tables built on the device (k_disp_tables), no host sync
+  // before the qcml loop: a single rank with pixels, unless H3D_BRENT=2 asks
+  // for gangs throughout (their task table the host builds from the segment
+  // bounds). Any number of live segments: the Brent mode is chosen on the
+  // device per qcml iteration (dual). The host builds the tables for the
+  // multi-rank driver, a call without pixels and H3D_BRENT=2.
+  bool dev_tables = false;
+  // dev_tables with H3D_BRENT=1: k_brent and k_brent_gang are both launched
+  // every qcml iteration and the DEVICE picks one by the live-segment count
+  // (one workgroup per segment while they fill the CUs, gangs for the tail
+  // iterations, whose few live segments left most CUs idle: cfg2's fourth
+  // iteration ran ~55 searches on 55 CUs for 0.36 ms); the gang task table
+  // comes from k_disp_tables. Cleared when a gang aborts.
+  bool dual = false;
+  HostStamps stamp;
+  // the pixels sorted by distance, replicate-major rows; pseudodata
+  int32_t *raw_s = nullptr, *dist_s = nullptr;
+  double *f_s = nullptr, *pd = nullptr;
+  int64_t* d_seg = nullptr;         // D + 1 segment bounds
+  std::vector<int64_t> seg_start;   // their host copy (host-built tables)
+  // chunk and segment tables, work list, per-segment state and results
+  int n_chunks = 0;
+  size_t max_items = 0;
+  int64_t *d_cs = nullptr, *d_lpx = nullptr;
+  int32_t *d_cl = nullptr, *d_cd = nullptr, *d_scb = nullptr, *d_sce = nullptr;
+  int32_t *d_nrep = nullptr, *d_repidx = nullptr;
+  SegState* d_st = nullptr;
+  int32_t *d_list = nullptr, *d_meta = nullptr, *d_slb = nullptr, *d_sle = nullptr;
+  double *d_partial = nullptr, *d_total = nullptr, *d_res = nullptr;
+  int *d_flags = nullptr, *d_bad = nullptr, *d_queue = nullptr;
+  GangTables gang;
+  // the pinned result zone (ctx->h_res): dispersions, final states, the
+  // device's distance check; h_meta: the polled work meta
+  int32_t* h_meta = nullptr;
+  double* h_resd = nullptr;
+  SegState* h_sst = nullptr;
+  int* h_bad = nullptr;
+  bool have_res = false;  // the results of the final poll are in h_res
+};
+
+// the equalize pass (heavy: q2qnbinom) over the active work list, then
+// (NLL: the multi-rank driver) the NLL-only pass (light)
+// (kFull: every condition has exactly M replicates -- k_disp_work's
+// replicate count is the constant M, see k_brent)
+template <int M, bool NLL, bool kFull = false>
+void launch_disp_work(const DispCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  auto launch = [&](auto k) {
+    hipLaunchKernelGGL(k, dim3(work_grid(ctx, k, c.max_items)), dim3(kBlock), 0, c.s, c.raw_s,
+                       c.f_s, c.pd, c.n, c.d_cs, c.d_cl, c.d_cd, c.C, c.d_repidx, c.d_nrep,
+                       c.d_st, c.d_flags, c.d_list, c.d_meta, c.d_partial, ctx->eq_static8);
+  };
+  {
+    ProfScope ps(ctx, "disp_work", 0, 1);
+    // the equalize register budget: 4 waves per SIMD up to M = 8 (the sweeps
+    // are in DESIGN.md, "Settled switches")
+    launch(k_disp_work<M, (M <= 8 ? 4 : 1), kEqualize, NLL, kFull>);
+  }
+  if constexpr (NLL) {
+    ProfScope ps(ctx, "disp_nll", 0);
+    launch(k_disp_work<M, 1, kNll>);
+  }
+}
+
+// grow-only pinned host buffer of the ctx (freed by h3d_close: a per-call
+// hipHostFree would synchronise the device)
+int pinned_grow(void** buf, size_t* cap, size_t bytes) {
+  if (*cap >= bytes) return 0;
+  if (*buf) (void)hipHostFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  HIP_TRY(hipHostMalloc(buf, bytes, hipHostMallocDefault));
+  *cap = bytes;
+  return 0;
+}
+
+// stable radix sort of (key, value) pairs over key bits [begin_bit, end_bit)
+template <typename K>
+int radix_sort_pairs(h3d_ctx* ctx, const K* keys_in, K* keys_out, const int32_t* vals_in,
+                     int32_t* vals_out, int64_t n, int begin_bit, int end_bit) {
+  size_t tmp_bytes = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in,
+                                             vals_out, (int)n, begin_bit, end_bit,
+                                             ctx->stream));
+  void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
+  if (!tmp) return fail(H3D_ENOMEM, "sort temp");
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_in, keys_out, vals_in,
+                                             vals_out, (int)n, begin_bit, end_bit,
+                                             ctx->stream));
+  return 0;
+}
+
+int validate_and_plan(DispCall& c, const int32_t* cond_of_rep, int estimator) {
+  h3d_ctx* ctx = c.ctx;
+  const int64_t n = c.n;
+  if (n < 0 || c.D < 1) return fail(H3D_EARG, "n=%lld D=%d", (long long)n, c.D);
+  if (n > 0 && (!c.d_raw || !c.d_f || !c.d_dist)) return fail(H3D_EARG, "null device input");
+  if (n >= (int64_t)1 << 31) return fail(H3D_EARG, "n=%lld exceeds 2^31 pixels per call", (long long)n);
+  if (estimator != H3D_EST_QCML)
+    return fail(H3D_EARG, "estimator %d: only qcml runs on the GPU path (the reference's cml/mme divide an int64 array in place and raise)", estimator);
+  if (int rc = check_cond(cond_of_rep, c.R, c.C, &c.nrep, &c.rep_idx)) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (std::getenv("H3D_DEBUG")) {
+    const hipError_t pe = hipGetLastError();
+    if (pe != hipSuccess)
+      fprintf(stderr, "[h3d] estimate_disp entry: pending HIP error %s\n", hipGetErrorString(pe));
+  }
+  c.s = ctx->stream;
+  c.S = c.D * c.C;
+  // (an M = 6 instantiation for cfg4's R_c = 6 measured equal to M = 8:
+  // 111.5 vs 110.5 ms equalize per step, profiles/r02/q2)
+  const int maxnr = *std::max_element(c.nrep.begin(), c.nrep.end());
+  c.mslot = maxnr <= 2 ? 2 : maxnr <= 4 ? 4 : maxnr <= 8 ? 8 : maxnr <= 16 ? 16 : 32;
+  // every condition has exactly mslot replicates: the kFull instantiations
+  // of the equalize pass and the Brent kernels (M = 2 only, see k_brent;
+  // H3D_NLL_FULL=0: never)
+  c.nll_full = ctx->nll_full && c.mslot == 2 &&
+               std::all_of(c.nrep.begin(), c.nrep.end(), [&](int r) { return r == c.mslot; });
+  c.dev_tables = !c.reduce && n > 0 && ctx->brent_gang != 2;
+  c.dual = c.dev_tables && ctx->brent_gang == 1;
+  return 0;
+}
+
+// One (distance, max, min count) order per condition: per condition a key
+// pass over its replicates' counts, a stable radix sort and a gather of just
+// those replicates' rows (profiles/r02/sortab). K = uint32_t while the
+// distance fits 16 bits: (distance, 8-bit min / max count codes), sorted over
+// end_bit + 16 bits (cfg2: 24 bits, three radix passes). (A stable scatter
+// into distance buckets, then each bucket sorted in LDS, gave the same order
+// but measured slower: prep 0.55 -> 1.19 ms per cfg2 step, r06aj / r06ak --
+// the scatter's 4-byte writes to ~250 buckets are uncoalesced (195 us) and
+// the LDS bitonic sorts LDS-bound (555 us); the radix passes stage their
+// scatter through LDS.) A distance outside the key's range, a negative one
+// included, saturates to the largest code, which is >= D: such pixels sort
+// behind every segment and the segment check rejects the call.
+template <typename K>
+int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* idx_out) {
+  h3d_ctx* ctx = c.ctx;
+  hipStream_t s = c.s;
+  const int64_t n = c.n;
+  const int R = c.R, C = c.C;
+  constexpr bool k32 = sizeof(K) == 4;
+  const int cbits = k32 ? 16 : 64 - end_bit;
+  const int sort_bits = k32 ? end_bit + 16 : 64;
+  int32_t* d_reps = (int32_t*)scratch(ctx, "sort_reps", (size_t)C * kMaxReps * 4);
+  if (!d_reps) return fail(H3D_ENOMEM, "sort buffers");
+  if (int rc = h2d_pinned(ctx, d_reps, c.rep_idx.data(), (size_t)C * kMaxReps * 4, s)) return rc;
+  // every condition of <= 2 replicates: one key pass for all of them, and
+  // the gathers read its packed (raw, f) records -- one 32-byte sector per
+  // pixel instead of a raw and an f line (k_dist_cond_keys_pack2)
+  const bool pack = k32 && c.mslot == 2;
+  int32_t* d_nrep = nullptr;
+  CondPack2* packed = nullptr;
+  if (pack) {
+    d_nrep = (int32_t*)scratch(ctx, "sort_nrep", (size_t)C * 4);
+    packed = (CondPack2*)scratch(ctx, "cond_pack2", (size_t)C * n * sizeof(CondPack2));
+    if (!d_nrep || !packed) return fail(H3D_ENOMEM, "packed gather rows");
+    if (int rc = h2d_pinned(ctx, d_nrep, c.nrep.data(), (size_t)C * 4, s)) return rc;
+  }
+  K* keys = (K*)scratch(ctx, "dkeys", (pack ? (size_t)C : 1) * n * sizeof(K));
+  K* keys_s = (K*)scratch(ctx, "dkeys_s", n * sizeof(K));
+  if (!keys || !keys_s) return fail(H3D_ENOMEM, "sort keys");
+  for (int cc = 0; cc < C; ++cc) {
+    const int32_t* reps_c = d_reps + cc * kMaxReps;
+    K* keys_c = pack ? keys + (size_t)cc * n : keys;
+    if (!pack)
+      hipLaunchKernelGGL(k_dist_cond_keys<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
+                         c.d_dist, c.d_raw, n, R, reps_c, c.nrep[cc], cbits, keys_c);
+    else if (cc == 0)  // (pack implies K = uint32_t)
+      hipLaunchKernelGGL(k_dist_cond_keys_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
+                         c.d_dist, c.d_raw, c.d_f, n, R, C, d_reps, d_nrep,
+                         reinterpret_cast<uint32_t*>(keys), packed);
+    if (int rc = radix_sort_pairs<K>(ctx, keys_c, keys_s, idx_in, idx_out, n, 0, sort_bits))
+      return rc;
+    if (cc == 0)
+      hipLaunchKernelGGL(k_key_dist<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
+                         (const K*)keys_s, n, cbits, c.dist_s);
+    SoaRows rows;
+    for (int j = 0; j < c.nrep[cc]; ++j) {
+      const int r = c.rep_idx[(size_t)cc * kMaxReps + j];
+      rows.raw[j] = c.raw_s + (size_t)r * n;
+      rows.f[j] = c.f_s + (size_t)r * n;
+    }
+    if (pack) {
+      hipLaunchKernelGGL(k_gather_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, idx_out,
+                         packed + (size_t)cc * n, n, c.nrep[cc], rows);
+      continue;
+    }
+    const int64_t tiles = (n + kGatherTile - 1) / kGatherTile;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)ctx->n_cu * 8));
+    hipLaunchKernelGGL(k_gather_cond_tile, dim3(grid), dim3(256), 0, s, idx_out, c.d_raw,
+                       c.d_f, n, R, reps_c, c.nrep[cc], rows);
+  }
+  return 0;
+}
+
+// Stage (n > 0): the pixels sorted by distance into SoA rows, the segment
+// bounds, and -- host-built tables -- the bounds on the host, checked.
+int sort_and_gather(DispCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  const int64_t n = c.n;
+  const int R = c.R, D = c.D;
+  ProfScope ps(ctx, "disp_prep", n);
+  int32_t* idx_in = (int32_t*)scratch(ctx, "idx_in", n * 4);
+  int32_t* idx_out = (int32_t*)scratch(ctx, "idx_out_c", n * 4);
+  c.dist_s = (int32_t*)scratch(ctx, "dist_s", n * 4);
+  c.raw_s = (int32_t*)scratch(ctx, "raw_s", n * R * 4);
+  c.f_s = (double*)scratch(ctx, "f_s", n * R * 8);
+  c.pd = (double*)scratch(ctx, "pd", n * R * 8);
+  c.d_seg = (int64_t*)scratch(ctx, "seg_start", (D + 1) * 8);
+  if (!idx_in || !idx_out || !c.dist_s || !c.raw_s || !c.f_s || !c.pd || !c.d_seg)
+    return fail(H3D_ENOMEM, "device allocation failed (n=%lld)", (long long)n);
+  hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, c.s, idx_in, n);
+  int end_bit = 1;
+  while ((1 << end_bit) <= D) ++end_bit;
+  if (int rc = end_bit <= 16 ? sort_by_condition<uint32_t>(c, end_bit, idx_in, idx_out)
+                             : sort_by_condition<uint64_t>(c, end_bit, idx_in, idx_out))
+    return rc;
+  hipLaunchKernelGGL(k_seg_bounds, dim3((D + 1 + 255) / 256), dim3(256), 0, c.s, c.dist_s, n,
+                     D, c.d_seg);
+  c.stamp("prep launched");
+  if (c.dev_tables) return 0;  // k_disp_tables checks the bounds
+  HIP_TRY(hipMemcpyAsync(c.seg_start.data(), c.d_seg, (D + 1) * 8, hipMemcpyDeviceToHost, c.s));
+  HIP_TRY(hipStreamSynchronize(c.s));
+  if (c.seg_start[0] != 0 || c.seg_start[D] != n) {
+    c.stamp("seg_start synced (dist check failed)");
+    // pixels with dist < 0 or >= D
+    return fail(H3D_EARG, "dist outside [0, %d)", D);
+  }
+  return 0;
+}
+
+// the chunk and segment tables the host builds from the segment bounds
+struct HostTables {
+  std::vector<int64_t> cs, lpx;
+  std::vector<int32_t> cl, cd, scb, sce;
+  std::vector<SegState> st;
+};
+
+int host_tables(DispCall& c, HostTables* t) {
+  h3d_ctx* ctx = c.ctx;
+  const int D = c.D, C = c.C, S = c.S;
+  const std::vector<int64_t>& seg_start = c.seg_start;
+  t->scb.resize(D);
+  t->sce.resize(D);
+  for (int d = 0; d < D; ++d) {
+    t->scb[d] = (int32_t)t->cl.size();
+    for (int64_t a = seg_start[d]; a < seg_start[d + 1]; a += kChunk) {
+      t->cs.push_back(a);
+      t->cl.push_back((int32_t)std::min<int64_t>(kChunk, seg_start[d + 1] - a));
+      t->cd.push_back(d);
+    }
+    t->sce[d] = (int32_t)t->cl.size();
+  }
+  c.n_chunks = (int)t->cl.size();
+  if (c.n_chunks == 0) {
+    // (n = 0: the staging below keeps room for one chunk and copies it)
+    t->cs.push_back(0);
+    t->cl.push_back(0);
+    t->cd.push_back(0);
+  }
+  // pixel counts per segment: this rank's, and over all ranks
+  t->lpx.resize(S);
+  for (int d = 0; d < D; ++d)
+    for (int cc = 0; cc < C; ++cc) t->lpx[d * C + cc] = seg_start[d + 1] - seg_start[d];
+  std::vector<double> cnt(t->lpx.begin(), t->lpx.end());
+  double* d_cnt = (double*)scratch(ctx, "seg_cnt", S * 8);
+  if (!d_cnt) return fail(H3D_ENOMEM, "seg_cnt");
+  if (c.reduce) {
+    HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), S * 8, hipMemcpyHostToDevice, c.s));
+    if (c.reduce(d_cnt, S, c.user)) return fail(H3D_EHIP, "allreduce callback failed");
+    HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, S * 8, hipMemcpyDeviceToHost, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));
+  }
+  t->st.resize(S);
+  for (int sg = 0; sg < S; ++sg)
+    seg_init(&t->st[sg], (long long)cnt[sg], c.nrep[sg % C], ctx->qcml_tol);
+  return 0;
+}
+
+// Stage: the per-call tables on the device -- host-built and uploaded, or
+// (dev_tables) only the design uploaded and the rest built by k_disp_tables
+// -- and the scratch of the qcml loop.
+int segment_tables(DispCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  hipStream_t s = c.s;
+  const int D = c.D, C = c.C, S = c.S;
+  HostTables t;
+  if (c.dev_tables)
+    c.n_chunks = (int)std::min<int64_t>(c.n / kChunk + D + 1, INT32_MAX);  // an upper bound
+  else if (int rc = host_tables(c, &t))
+    return rc;
+  // the tables go up as ONE copy from a pinned staging buffer (nine pageable
+  // copies cost ~0.3 ms of host-side gaps per cfg2 step: each staged and
+  // launched its own blit)
+  std::vector<int32_t> nrep32(c.nrep.begin(), c.nrep.end());
+  struct Part {
+    const void* src;
+    size_t bytes, off;
+  };
+  // (dev_tables: the chunk / segment tables are k_disp_tables' outputs, only
+  // their room is reserved and nothing of them is copied)
+  const size_t nch = (size_t)std::max(c.n_chunks, 1);
+  Part parts[] = {{t.cs.data(), nch * 8, 0},
+                  {t.cl.data(), nch * 4, 0},
+                  {t.cd.data(), nch * 4, 0},
+                  {t.scb.data(), (size_t)D * 4, 0},
+                  {t.sce.data(), (size_t)D * 4, 0},
+                  {nrep32.data(), (size_t)C * 4, 0},
+                  {c.rep_idx.data(), c.rep_idx.size() * 4, 0},
+                  {t.st.data(), (size_t)S * sizeof(SegState), 0},
+                  {t.lpx.data(), (size_t)S * 8, 0}};
+  size_t blob = 0;
+  for (Part& q : parts) {
+    q.off = blob;
+    blob += (q.bytes + 255) & ~(size_t)255;
+  }
+  // the parts that go up: all of them, or (dev_tables) nrep + rep_idx only
+  const int q_lo = c.dev_tables ? 5 : 0, q_hi = c.dev_tables ? 7 : 9;
+  const size_t up_lo = parts[q_lo].off, up_hi = q_hi < 9 ? parts[q_hi].off : blob;
+  if (!ctx->h_stage_done)
+    HIP_TRY(hipEventCreateWithFlags(&ctx->h_stage_done, hipEventDisableTiming));
+  else
+    HIP_TRY(hipEventSynchronize(ctx->h_stage_done));  // the previous copy has read it
+  if (int rc = pinned_grow(&ctx->h_stage, &ctx->h_stage_bytes, blob)) return rc;
+  char* d_blob = (char*)scratch(ctx, "disp_tables", blob);
+  if (!d_blob) return fail(H3D_ENOMEM, "disp tables");
+  for (int qi = q_lo; qi < q_hi; ++qi)
+    if (parts[qi].bytes)
+      std::memcpy((char*)ctx->h_stage + parts[qi].off, parts[qi].src, parts[qi].bytes);
+  HIP_TRY(hipMemcpyAsync(d_blob + up_lo, (char*)ctx->h_stage + up_lo, up_hi - up_lo,
+                         hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(ctx->h_stage_done, s));
+  c.d_cs = (int64_t*)(d_blob + parts[0].off);
+  c.d_cl = (int32_t*)(d_blob + parts[1].off);
+  c.d_cd = (int32_t*)(d_blob + parts[2].off);
+  c.d_scb = (int32_t*)(d_blob + parts[3].off);
+  c.d_sce = (int32_t*)(d_blob + parts[4].off);
+  c.d_nrep = (int32_t*)(d_blob + parts[5].off);
+  c.d_repidx = (int32_t*)(d_blob + parts[6].off);
+  c.d_st = (SegState*)(d_blob + parts[7].off);
+  c.d_lpx = (int64_t*)(d_blob + parts[8].off);
+  c.max_items = nch * C;
+  c.d_list = (int32_t*)scratch(ctx, "work_list", c.max_items * 4);
+  // len, active, eq_len, live; k_disp_work's task heads (kTaskHeadStride apart)
+  c.d_meta = (int32_t*)scratch(ctx, "work_meta", kWorkMetaInts * 4);
+  c.d_slb = (int32_t*)scratch(ctx, "seg_lb", S * 4);
+  c.d_sle = (int32_t*)scratch(ctx, "seg_le", S * 4);
+  c.d_partial = (double*)scratch(ctx, "partial", c.max_items * 8 * kWavesPerBlock);
+  c.d_total = (double*)scratch(ctx, "seg_total", S * 8);
+  c.d_flags = (int*)scratch(ctx, "seg_flags", S * 4);
+  c.d_res = (double*)scratch(ctx, "seg_result", S * 8);
+  c.d_bad = (int*)scratch(ctx, "dist_bad", 4);
+  if (!c.d_list || !c.d_meta || !c.d_slb || !c.d_sle || !c.d_partial || !c.d_total ||
+      !c.d_flags || !c.d_res || !c.d_bad)
+    return fail(H3D_ENOMEM, "disp scratch");
+  if (!c.dev_tables) {
+    HIP_TRY(hipMemsetAsync(c.d_flags, 0, S * 4, s));  // else k_disp_tables
+  } else {
+    if (c.dual)
+      if (int rc = with_width(c.mslot, false, [&](auto m, auto) {
+            return gang_setup_dev<decltype(m)::value>(ctx, c.n, D, C, &c.gang);
+          }))
+        return rc;
+    hipLaunchKernelGGL(k_disp_tables, dim3(1), dim3(1024), 0, s, c.d_seg, D, C, c.n, c.d_nrep,
+                       c.d_cs, c.d_cl, c.d_cd, c.d_scb, c.d_sce, c.d_st, c.d_lpx, c.d_bad,
+                       c.dual ? c.gang.P : (int64_t)1, c.dual ? c.gang.task_seg : nullptr,
+                       c.dual ? c.gang.task_g : nullptr, ctx->qcml_tol, c.dual ? c.gang.T : 0,
+                       c.d_flags, c.dual ? c.gang.abort : nullptr);
+    dbg_launch("k_disp_tables");
+  }
+  c.stamp("tables uploaded");
+  return 0;
+}
+
+// k_seg_update: (step, multi-rank) advances every active segment's state
+// machine with its reduced total, then rebuilds the active work list; init:
+// the first list of a call. It also zeroes the single-rank Brent kernels'
+// work queues.
+void launch_seg_update(DispCall& c, int init, int step) {
+  ProfScope ps(c.ctx, "disp_update", 0, init ? 3 : 2);  // (the first list is not timed)
+  hipLaunchKernelGGL(k_seg_update, dim3(1), dim3(1024), 0, c.s, c.d_st, c.d_total, c.d_flags,
+                     c.S, c.C, c.d_nrep, c.d_scb, c.d_sce, c.d_list, c.d_slb, c.d_sle, c.d_res,
+                     c.d_meta, init, step, c.d_lpx, c.ctx->work_count,
+                     step ? nullptr : c.d_queue, c.dual ? c.gang.P : (int64_t)1,
+                     c.dual ? c.gang.task_seg : nullptr, c.dual ? c.gang.task_g : nullptr);
+}
+
+// Stage: the first active list and the pinned zone the results land in.
+int start_qcml(DispCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  c.d_queue = (int*)scratch(ctx, "brent_queue", 2 * sizeof(int));
+  if (!c.d_queue) return fail(H3D_ENOMEM, "brent queue");
+  launch_seg_update(c, 1, 0);
+  if (!ctx->h_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_meta, 32, hipHostMallocDefault));
+  c.h_meta = ctx->h_meta;
+  const size_t res_bytes = (size_t)c.S * 8 + (size_t)c.S * sizeof(SegState) + 8;
+  if (int rc = pinned_grow(&ctx->h_res, &ctx->h_res_bytes, res_bytes)) return rc;
+  c.h_resd = (double*)ctx->h_res;
+  c.h_sst = (SegState*)(c.h_resd + c.S);
+  c.h_bad = (int*)(c.h_sst + c.S);
+  *c.h_bad = 0;
+  return 0;
+}
+
+// the results into the pinned zone (enqueued; the caller waits)
+hipError_t copy_results(DispCall& c) {
+  hipError_t e = hipMemcpyAsync(c.h_resd, c.d_res, (size_t)c.S * 8, hipMemcpyDeviceToHost, c.s);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c.h_sst, c.d_st, (size_t)c.S * sizeof(SegState), hipMemcpyDeviceToHost,
+                       c.s);
+  if (e == hipSuccess && c.dev_tables)
+    e = hipMemcpyAsync(c.h_bad, c.d_bad, 4, hipMemcpyDeviceToHost, c.s);
+  return e;
+}
+
+// One poll of the single-rank loop: the live-segment count and,
+// speculatively, what follows a final poll -- the result copies (pinned) and
+// the requested smoother behind them, so a final poll costs one host round
+// trip (r03s trace: ~0.12 ms of host gaps after the fifth iteration); a poll
+// that finds live segments simply runs them, and a later poll redoes both.
+int poll_single_rank(DispCall& c, bool gangs) {
+  h3d_ctx* ctx = c.ctx;
+  hipEvent_t copied = ev_get(ctx);
+  int rc = 0;
+  if (hipMemcpyAsync(c.h_meta, c.d_meta, 16, hipMemcpyDeviceToHost, c.s) != hipSuccess ||
+      (gangs && hipMemcpyAsync(c.h_meta + 4, c.gang.abort, 4, hipMemcpyDeviceToHost, c.s) !=
+                    hipSuccess) ||
+      copy_results(c) != hipSuccess || hipEventRecord(copied, c.s) != hipSuccess) {
+    ctx->event_pool.push_back(copied);
+    return fail(H3D_EHIP, "disp round copies failed: %s", hipGetErrorString(hipGetLastError()));
+  }
+  // (speculatively only where the smoother is the device's, enqueued without
+  // a wait; the host smoother of D > kTableMaxD runs once, on the final
+  // result -- on an intermediate poll it would block and could reject a
+  // table that is not final)
+  if (c.treq && c.D <= kTableMaxD)
+    rc = h3d_disp_tables_dev(ctx, c.d_res, c.D, c.C, c.treq->weighted, c.treq->frac,
+                             c.treq->aff, c.treq->d_tables);
+  const hipError_t ce = hipEventSynchronize(copied);
+  ctx->event_pool.push_back(copied);
+  if (rc) return rc;
+  if (ce != hipSuccess) return fail(H3D_EHIP, "disp round sync failed: %s", hipGetErrorString(ce));
+  c.have_res = true;
+  c.stamp("poll");
+  return 0;
+}
+
+// Stage, single rank: one equalize pass per qcml iteration over every segment
+// that needs one, then k_brent (or gangs, k_brent_gang) runs each such
+// segment's whole Brent search in-kernel, then k_seg_update rebuilds the
+// equalize list. The host polls the live-segment count every `batch`
+// iterations (an iteration with nothing to do costs three empty launches).
+int qcml_single_rank(DispCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  if (c.n == 0) {
+    c.d_seg = (int64_t*)scratch(ctx, "seg_start", (c.D + 1) * 8);
+    if (!c.d_seg) return fail(H3D_ENOMEM, "brent scratch");
+    HIP_TRY(hipMemsetAsync(c.d_seg, 0, (c.D + 1) * 8, c.s));
+  }
+  // H3D_BRENT=2 (host-built tables): every search in gangs
+  bool use_gang = ctx->brent_gang == 2 && c.n > 0;
+  if (use_gang) {
+    const int grc = with_width(c.mslot, false, [&](auto m, auto) {
+      return gang_setup<decltype(m)::value>(ctx, c.seg_start, c.D, c.C, &c.gang);
+    });
+    if (grc == 1) use_gang = false;
+    else if (grc) return grc;
+  }
+  // first poll after 5 iterations (cfg2's searches end after 5; a poll is a
+  // host sync plus the relaunch latency, ~50 us of idle GPU -- r03 host
+  // stamps), then every 2
+  int rounds = 0, batch = 5;
+  while (true) {
+    for (int b = 0; b < batch; ++b) {
+      dbg_launch("before qcml iteration");
+      with_width(c.mslot, c.nll_full, [&](auto m, auto full) {
+        constexpr int M = decltype(m)::value;
+        constexpr bool kFull = decltype(full)::value;
+        auto brent = [&](const int32_t* gate_meta, int live_min, const int* gang_abort) {
+          launch_brent<M, kFull>(ctx, c.pd, c.n, c.d_seg, c.S, c.C, c.d_repidx, c.d_nrep,
+                                 c.d_st, c.d_flags, c.d_res, c.d_queue, gate_meta, live_min,
+                                 gang_abort, true);
+        };
+        auto gang = [&](const int32_t* gate_meta, int live_max) {
+          launch_brent_gang<M, kFull>(ctx, c.pd, c.n, c.d_seg, c.S, c.C, c.d_repidx, c.d_nrep,
+                                      c.d_st, c.d_flags, c.d_res, c.d_queue + 1, c.gang,
+                                      gate_meta, live_max, true);
+        };
+        launch_disp_work<M, false, kFull>(c);
+        dbg_launch("equalize");
+        if (c.dual) {
+          brent(c.d_meta, ctx->n_cu, c.gang.abort);
+          dbg_launch("k_brent (dual)");
+          gang(c.d_meta, ctx->n_cu);
+          dbg_launch("k_brent_gang (dual)");
+        } else if (use_gang) {
+          gang(nullptr, 0);
+        } else {
+          brent(nullptr, 0, nullptr);
+        }
+      });
+      launch_seg_update(c, 0, 0);
+      ++rounds;
+    }
+    const bool gangs = use_gang || c.dual;
+    if (int rc = poll_single_rank(c, gangs)) return rc;
+    if (std::getenv("H3D_DEBUG"))
+      fprintf(stderr, "[h3d] qcml iterations=%d live_segments=%d gang=%d abort=%d\n", rounds,
+              c.h_meta[3], use_gang ? 1 : c.dual ? 2 : 0, gangs ? c.h_meta[4] : 0);
+    if (c.dual && c.h_meta[4]) {
+      // a gang aborted: k_brent (gated on the same flag) already took over
+      // the following iterations on the device; launch it alone from here
+      c.dual = false;
+      ctx->gang_aborts += 1;
+    }
+    if (use_gang && c.h_meta[4]) {
+      // a gang's wait timed out (CUs held elsewhere): its segments stayed
+      // in kEqualize and repeat their iteration; finish with k_brent
+      use_gang = false;
+      ctx->gang_aborts += 1;
+      continue;
+    }
+    if (c.h_meta[3] == 0) return 0;
+    if (rounds > 2000) return fail(H3D_ENOCONV, "estimate_disp did not terminate");
+    batch = 2;
+  }
+}
+
+// Stage, multi-rank: per Brent evaluation an equalize / NLL pass, this
+// rank's per-segment sums (k_seg_reduce), the cross-rank all-reduce, and
+// k_seg_update stepping the (identical) state machines. Polled after 2, 4,
+// then every 8 rounds.
+int qcml_multi_rank(DispCall& c) {
+  int rounds = 0, batch = 2;
+  while (true) {
+    for (int b = 0; b < batch; ++b) {
+      // every width the single-rank driver picks (mslot 2 fell through to
+      // the M = 32 instantiation here: 13.1 vs 5.5 ms of equalize per cfg2
+      // step, bench --noop-reduce)
+      with_width(c.mslot, false,
+                 [&](auto m, auto) { launch_disp_work<decltype(m)::value, true>(c); });
+      {
+        ProfScope ps(c.ctx, "disp_reduce", 0);
+        hipLaunchKernelGGL(k_seg_reduce, dim3((c.S + 3) / 4), dim3(256), 0, c.s, c.d_partial,
+                           c.d_slb, c.d_sle, c.S, c.d_total, nullptr, c.d_flags, c.d_nrep, c.C,
+                           c.d_res);
+      }
+      if (c.reduce(c.d_total, c.S, c.user)) return fail(H3D_EHIP, "allreduce callback failed");
+      launch_seg_update(c, 0, 1);
+      ++rounds;
+    }
+    if (hipMemcpyAsync(c.h_meta, c.d_meta, 16, hipMemcpyDeviceToHost, c.s) != hipSuccess ||
+        hipStreamSynchronize(c.s) != hipSuccess)
+      return fail(H3D_EHIP, "disp round sync failed: %s", hipGetErrorString(hipGetLastError()));
+    if (std::getenv("H3D_DEBUG"))
+      fprintf(stderr, "[h3d] disp rounds=%d active_items=%d live_segments=%d\n", rounds,
+              c.h_meta[1], c.h_meta[3]);
+    // terminate on the genome-wide live-segment count (identical on every
+    // rank), not on this rank's own work-list length: a rank without pixels
+    // in the still-active segments must keep joining the collective reduce
+    if (c.h_meta[3] == 0) return 0;
+    if (rounds > 200000) return fail(H3D_ENOCONV, "estimate_disp did not terminate");
+    batch = std::min(batch * 2, 8);
+  }
+}
+
+// Stage: the results to the caller, the kernels' status, the smoother.
+int collect_results(DispCall& c, double* disp_per_dist, int32_t* seg_flags_out) {
+  h3d_ctx* ctx = c.ctx;
+  const TableReq* treq = c.treq;
+  // a launch error of the qcml loop is this call's, not a later call's
+  HIP_TRY(hipGetLastError());
+  if (!c.have_res) {
+    // (the multi-rank path) the results into the pinned zone; the smoother
+    // runs behind the copies, the host waits for the copies only
+    HIP_TRY(copy_results(c));
+    hipEvent_t copied = ev_get(ctx);
+    HIP_TRY(hipEventRecord(copied, c.s));
+    const int trc = treq ? h3d_disp_tables_dev(ctx, c.d_res, c.D, c.C, treq->weighted,
+                                               treq->frac, treq->aff, treq->d_tables)
+                         : 0;
+    const hipError_t e = hipEventSynchronize(copied);
+    ctx->event_pool.push_back(copied);
+    if (trc) return trc;
+    if (e != hipSuccess) return fail(H3D_EHIP, "result copy: %s", hipGetErrorString(e));
+  }
+  std::memcpy(disp_per_dist, c.h_resd, (size_t)c.S * 8);
+  ctx->last_S = c.S;
+  c.stamp("results");
+  if (c.dev_tables && *c.h_bad) return fail(H3D_EARG, "dist outside [0, %d)", c.D);
+  int all = 0;
+  for (int sg = 0; sg < c.S; ++sg) {
+    all |= c.h_sst[sg].flags;
+    if (seg_flags_out) seg_flags_out[sg] = c.h_sst[sg].flags;
+  }
+  if (const int frc = flags_to_code(all)) return frc;
+  if (c.have_res && treq && c.D > kTableMaxD)
+    // the host smoother (h3d_disp_tables_dev's D > kTableMaxD branch), once,
+    // on the final result
+    return h3d_disp_tables_dev(ctx, c.d_res, c.D, c.C, treq->weighted, treq->frac, treq->aff,
+                               treq->d_tables);
+  return 0;
+}
+
+int disp_per_dist_core(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
+                       const int32_t* d_dist, int64_t n, int R, int C,
+                       const int32_t* cond_of_rep, int D, int estimator,
+                       double* disp_per_dist, int32_t* seg_flags_out,
+                       h3d_allreduce_fn reduce, void* user, const TableReq* treq) {
+  if (!ctx || !cond_of_rep || !disp_per_dist) return fail(H3D_EARG, "null argument");
+  DispCall c;
+  c.ctx = ctx;
+  c.d_raw = d_raw;
+  c.d_f = d_f;
+  c.d_dist = d_dist;
+  c.n = n;
+  c.R = R;
+  c.C = C;
+  c.D = D;
+  c.reduce = reduce;
+  c.user = user;
+  c.treq = treq;
+  if (int rc = validate_and_plan(c, cond_of_rep, estimator)) return rc;
+  c.seg_start.assign(D + 1, 0);
+  if (n > 0)
+    if (int rc = sort_and_gather(c)) return rc;
+  c.stamp("seg_start synced");
+  if (int rc = segment_tables(c)) return rc;
+  if (int rc = start_qcml(c)) return rc;
+  if (int rc = reduce ? qcml_multi_rank(c) : qcml_single_rank(c)) return rc;
+  return collect_results(c, disp_per_dist, seg_flags_out);
 }
 
 }  // namespace
@@ -547,20 +1146,12 @@ h3d_ctx* h3d_open(int device) {
     return nullptr;
   }
   ctx->stream = ctx->own;
-  if (const char* e = std::getenv("H3D_DISP_W")) ctx->disp_w = std::atoi(e);
-  if (const char* e = std::getenv("H3D_DISP_SORT")) ctx->disp_sort = std::atoi(e);
-  if (const char* e = std::getenv("H3D_NLL_W")) ctx->nll_w = std::atoi(e);
-  if (const char* e = std::getenv("H3D_DISP_W8")) ctx->disp_w8 = std::atoi(e);
-  if (const char* e = std::getenv("H3D_DISP_W2")) ctx->disp_w2 = std::atoi(e);
-  if (const char* e = std::getenv("H3D_PACK_GATHER")) ctx->pack_gather = std::atoi(e);
   if (const char* e = std::getenv("H3D_EQ_STATIC8"))
     ctx->eq_static8 = std::max(0, std::min(8, std::atoi(e)));
-  if (const char* e = std::getenv("H3D_DISP_M2")) ctx->disp_m2 = std::atoi(e);
   if (const char* e = std::getenv("H3D_BRENT")) ctx->brent_gang = std::atoi(e);
   if (const char* e = std::getenv("H3D_BRENT_LDS_KB")) ctx->brent_lds_kb = std::atoi(e);
   if (const char* e = std::getenv("H3D_NLL_FULL")) ctx->nll_full = std::atoi(e);
   if (const char* e = std::getenv("H3D_GANG_P")) ctx->gang_px = std::atoi(e);
-  if (const char* e = std::getenv("H3D_DEV_SEG_TABLES")) ctx->dev_seg_tables = std::atoi(e);
   if (hipMalloc((void**)&ctx->work_count, 2 * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(ctx->work_count, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {
     (void)hipStreamDestroy(ctx->own);
@@ -667,32 +1258,8 @@ int h3d_profile_read(h3d_ctx* ctx, const char* name, double* total_ms,
 }
 
 // ---------------------------------------------------------------------------
-// estimate_disp
+// estimate_disp (the driver: disp_per_dist_core, above)
 // ---------------------------------------------------------------------------
-
-namespace {
-// H3D_DEBUG: the first launch error of the estimate_disp driver, by site
-void dbg_launch(const char* where) {
-  static const bool on = std::getenv("H3D_DEBUG") != nullptr;
-  if (!on) return;
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) fprintf(stderr, "[h3d] launch error at %s: %s\n", where, hipGetErrorString(e));
-}
-
-// h3d_estimate_disp_dev's request: the smoothed tables of the result, on the
-// device, enqueued behind the result copies
-struct TableReq {
-  int weighted;
-  double frac, aff;
-  double* d_tables;
-};
-
-int disp_per_dist_core(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
-                       const int32_t* d_dist, int64_t n, int R, int C,
-                       const int32_t* cond_of_rep, int D, int estimator,
-                       double* disp_per_dist, int32_t* seg_flags_out,
-                       h3d_allreduce_fn reduce, void* user, const TableReq* treq);
-}  // namespace
 
 int h3d_disp_per_dist_dev(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
                           const int32_t* d_dist, int64_t n, int R, int C,
@@ -713,629 +1280,6 @@ int h3d_estimate_disp_dev(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
   return disp_per_dist_core(ctx, d_raw, d_f, d_dist, n, R, C, cond_of_rep, D, H3D_EST_QCML,
                             disp_per_dist, seg_flags_out, nullptr, nullptr, &req);
 }
-
-namespace {
-int disp_per_dist_core(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
-                       const int32_t* d_dist, int64_t n, int R, int C,
-                       const int32_t* cond_of_rep, int D, int estimator,
-                       double* disp_per_dist, int32_t* seg_flags_out,
-                       h3d_allreduce_fn reduce, void* user, const TableReq* treq) {
-  if (!ctx || !cond_of_rep || !disp_per_dist) return fail(H3D_EARG, "null argument");
-  if (n < 0 || D < 1) return fail(H3D_EARG, "n=%lld D=%d", (long long)n, D);
-  if (n > 0 && (!d_raw || !d_f || !d_dist)) return fail(H3D_EARG, "null device input");
-  if (n >= (int64_t)1 << 31) return fail(H3D_EARG, "n=%lld exceeds 2^31 pixels per call", (long long)n);
-  if (estimator != H3D_EST_QCML)
-    return fail(H3D_EARG, "estimator %d: only qcml runs on the GPU path (the reference's cml/mme divide an int64 array in place and raise)", estimator);
-  std::vector<int> nrep;
-  std::vector<int32_t> rep_idx;
-  if (int rc = check_cond(cond_of_rep, R, C, &nrep, &rep_idx)) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
-  if (std::getenv("H3D_DEBUG")) {
-    const hipError_t pe = hipGetLastError();
-    if (pe != hipSuccess)
-      fprintf(stderr, "[h3d] estimate_disp entry: pending HIP error %s\n", hipGetErrorString(pe));
-  }
-  hipStream_t s = ctx->stream;
-  const int S = D * C;
-  const int maxnr = *std::max_element(nrep.begin(), nrep.end());
-  HostStamps stamp;
-  // the per-call tables built on the device (k_disp_tables), no host sync
-  // before the qcml loop -- single rank, and enough segments that the Brent
-  // searches need no gangs (whose task tables the host builds from the
-  // segment bounds)
-  // (any number of live segments: the Brent mode -- one workgroup per
-  // segment or gangs -- is chosen on the device per qcml iteration, so a rank
-  // of the distance re-shard, whose ~D / world live segments leave CUs idle,
-  // needs no host-built gang tables either; r03z: its N = 8 cfg3 share 13.9
-  // ms per step with the host tables, 13.9 with these)
-  const bool dev_tables = ctx->dev_seg_tables && !reduce && n > 0 && ctx->brent_gang != 2;
-
-  // 1. stable sort of the pixels by distance, SoA gather
-  std::vector<int64_t> seg_start(D + 1, 0);
-  int32_t *raw_s = nullptr, *dist_s = nullptr;
-  double *f_s = nullptr, *pd = nullptr;
-  if (n > 0) {
-    ProfScope ps(ctx, "disp_prep", n);
-    int32_t* idx_in = (int32_t*)scratch(ctx, "idx_in", n * 4);
-    int32_t* idx_out = (int32_t*)scratch(ctx, "idx_out", n * 4);
-    dist_s = (int32_t*)scratch(ctx, "dist_s", n * 4);
-    raw_s = (int32_t*)scratch(ctx, "raw_s", n * R * 4);
-    f_s = (double*)scratch(ctx, "f_s", n * R * 8);
-    pd = (double*)scratch(ctx, "pd", n * R * 8);
-    int64_t* d_seg = (int64_t*)scratch(ctx, "seg_start", (D + 1) * 8);
-    if (!idx_in || !idx_out || !dist_s || !raw_s || !f_s || !pd || !d_seg)
-      return fail(H3D_ENOMEM, "device allocation failed (n=%lld)", (long long)n);
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, idx_in, n);
-    int end_bit = 1;
-    while ((1 << end_bit) <= D) ++end_bit;
-    size_t tmp_bytes = 0;
-    if (ctx->disp_sort == 2) {
-      // one (distance, max, min count) order per condition: per condition a
-      // key pass over its replicates' counts, a radix sort, and a tiled
-      // gather of just those replicates' row slices (k_gather_cond_tile)
-      idx_out = (int32_t*)scratch(ctx, "idx_out_c", (size_t)n * 4);
-      int32_t* d_reps = (int32_t*)scratch(ctx, "sort_reps", (size_t)C * kMaxReps * 4);
-      if (!idx_out || !d_reps) return fail(H3D_ENOMEM, "sort buffers");
-      if (int rc = h2d_pinned(ctx, d_reps, rep_idx.data(), (size_t)C * kMaxReps * 4, s))
-        return rc;
-      const bool k32 = end_bit <= 16;
-      // 32-bit keys: (distance, 8-bit min / max count codes), sorted over
-      // end_bit + 16 bits (cfg2: 24 bits, three radix passes). (A stable
-      // scatter into distance buckets, then each bucket sorted in LDS, gave
-      // the same order but measured slower: prep 0.55 -> 1.19 ms per cfg2
-      // step, r06aj / r06ak -- the scatter's 4-byte writes to ~250 buckets
-      // are uncoalesced (195 us) and the LDS bitonic sorts LDS-bound (555
-      // us); the radix passes stage their scatter through LDS.)
-      const int cbits = k32 ? 16 : 64 - end_bit;
-      const int sort_bits = k32 ? end_bit + 16 : 64;
-      // every condition of <= 2 replicates: one key pass for all of them,
-      // packed (raw, f) records for the gathers (k_dist_cond_keys_pack2)
-      const bool pack = k32 && maxnr <= 2 && ctx->pack_gather;
-      int32_t* d_nrep = nullptr;
-      CondPack2* packed = nullptr;
-      if (pack) {
-        d_nrep = (int32_t*)scratch(ctx, "sort_nrep", (size_t)C * 4);
-        packed = (CondPack2*)scratch(ctx, "cond_pack2", (size_t)C * n * sizeof(CondPack2));
-        if (!d_nrep || !packed) return fail(H3D_ENOMEM, "packed gather rows");
-        if (int rc = h2d_pinned(ctx, d_nrep, nrep.data(), (size_t)C * 4, s)) return rc;
-      }
-      void* keys = scratch(ctx, "dkeys", (pack ? (size_t)C : 1) * n * (k32 ? 4 : 8));
-      void* keys_s = scratch(ctx, "dkeys_s", n * (k32 ? 4 : 8));
-      if (!keys || !keys_s) return fail(H3D_ENOMEM, "sort keys");
-      for (int c = 0; c < C; ++c) {
-        const int32_t* reps_c = d_reps + c * kMaxReps;
-        uint32_t* keys_c = pack ? (uint32_t*)keys + (size_t)c * n : (uint32_t*)keys;
-        if (pack) {
-          if (c == 0)
-            hipLaunchKernelGGL(k_dist_cond_keys_pack2, dim3(grid_for(ctx, n)), dim3(kBlock),
-                               0, s, d_dist, d_raw, d_f, n, R, C, d_reps, d_nrep, keys_c,
-                               packed);
-        } else if (k32) {
-          hipLaunchKernelGGL(k_dist_cond_keys<uint32_t>, dim3(grid_for(ctx, n)),
-                             dim3(kBlock), 0, s, d_dist, d_raw, n, R, reps_c, nrep[c],
-                             cbits, keys_c);
-        }
-        if (k32) {
-          HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_c,
-                                                     (uint32_t*)keys_s, idx_in, idx_out,
-                                                     (int)n, 0, sort_bits, s));
-          void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
-          if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-          HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_c,
-                                                     (uint32_t*)keys_s, idx_in, idx_out,
-                                                     (int)n, 0, sort_bits, s));
-          if (c == 0)
-            hipLaunchKernelGGL(k_key_dist<uint32_t>, dim3(grid_for(ctx, n)), dim3(kBlock),
-                               0, s, (const uint32_t*)keys_s, n, cbits, dist_s);
-        } else {
-          hipLaunchKernelGGL(k_dist_cond_keys<uint64_t>, dim3(grid_for(ctx, n)),
-                             dim3(kBlock), 0, s, d_dist, d_raw, n, R, reps_c, nrep[c],
-                             cbits, (uint64_t*)keys);
-          HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (uint64_t*)keys,
-                                                     (uint64_t*)keys_s, idx_in, idx_out,
-                                                     (int)n, 0, 64, s));
-          void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
-          if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-          HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, (uint64_t*)keys,
-                                                     (uint64_t*)keys_s, idx_in, idx_out,
-                                                     (int)n, 0, 64, s));
-          if (c == 0)
-            hipLaunchKernelGGL(k_key_dist<uint64_t>, dim3(grid_for(ctx, n)), dim3(kBlock),
-                               0, s, (const uint64_t*)keys_s, n, cbits, dist_s);
-        }
-        SoaRows rows;
-        for (int j = 0; j < nrep[c]; ++j) {
-          const int r = rep_idx[(size_t)c * kMaxReps + j];
-          rows.raw[j] = raw_s + (size_t)r * n;
-          rows.f[j] = f_s + (size_t)r * n;
-        }
-        if (pack) {
-          hipLaunchKernelGGL(k_gather_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                             idx_out, packed + (size_t)c * n, n, nrep[c], rows);
-          continue;
-        }
-        const int64_t tiles = (n + kGatherTile - 1) / kGatherTile;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)ctx->n_cu * 8));
-        hipLaunchKernelGGL(k_gather_cond_tile, dim3(grid), dim3(256), 0, s, idx_out, d_raw,
-                           d_f, n, R, reps_c, nrep[c], rows);
-      }
-    } else if (ctx->disp_sort == 1 && end_bit <= 16) {
-      // (distance, total count) keys: same segments, less lane divergence;
-      // 32-bit keys (16 count bits) whenever the distance fits 16 bits
-      constexpr int cbits = 16;
-      uint32_t* keys = (uint32_t*)scratch(ctx, "dkeys", n * 4);
-      uint32_t* keys_s = (uint32_t*)scratch(ctx, "dkeys_s", n * 4);
-      if (!keys || !keys_s) return fail(H3D_ENOMEM, "sort keys");
-      hipLaunchKernelGGL(k_dist_count_keys<uint32_t>, dim3(grid_for(ctx, n)), dim3(kBlock),
-                         0, s, d_dist, d_raw, n, R, cbits, keys);
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_s,
-                                                 idx_in, idx_out, (int)n, 0,
-                                                 cbits + end_bit, s));
-      void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
-      if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_s, idx_in,
-                                                 idx_out, (int)n, 0, cbits + end_bit, s));
-      hipLaunchKernelGGL(k_key_dist<uint32_t>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         keys_s, n, cbits, dist_s);
-    } else if (ctx->disp_sort == 1) {
-      constexpr int cbits = 32;
-      uint64_t* keys = (uint64_t*)scratch(ctx, "dkeys", n * 8);
-      uint64_t* keys_s = (uint64_t*)scratch(ctx, "dkeys_s", n * 8);
-      if (!keys || !keys_s) return fail(H3D_ENOMEM, "sort keys");
-      hipLaunchKernelGGL(k_dist_count_keys<uint64_t>, dim3(grid_for(ctx, n)), dim3(kBlock),
-                         0, s, d_dist, d_raw, n, R, cbits, keys);
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys_s,
-                                                 idx_in, idx_out, (int)n, 0,
-                                                 cbits + end_bit, s));
-      void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
-      if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys_s, idx_in,
-                                                 idx_out, (int)n, 0, cbits + end_bit, s));
-      hipLaunchKernelGGL(k_key_dist<uint64_t>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         keys_s, n, cbits, dist_s);
-    } else {
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_dist, dist_s,
-                                                 idx_in, idx_out, (int)n, 0, end_bit, s));
-      void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
-      if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, d_dist, dist_s, idx_in,
-                                                 idx_out, (int)n, 0, end_bit, s));
-    }
-    if (ctx->disp_sort != 2) {
-      SoaRows rows;
-      for (int r = 0; r < R; ++r) {
-        rows.raw[r] = raw_s + (size_t)r * n;
-        rows.f[r] = f_s + (size_t)r * n;
-      }
-      hipLaunchKernelGGL(k_gather_soa, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         idx_out, d_raw, d_f, n, R, rows);
-    }
-    hipLaunchKernelGGL(k_seg_bounds, dim3((D + 1 + 255) / 256), dim3(256), 0, s,
-                       dist_s, n, D, d_seg);
-    if (!dev_tables) {
-      HIP_TRY(hipMemcpyAsync(seg_start.data(), d_seg, (D + 1) * 8,
-                             hipMemcpyDeviceToHost, s));
-      stamp("prep launched");
-      HIP_TRY(hipStreamSynchronize(s));
-      if (seg_start[0] != 0 || seg_start[D] != n) {
-        stamp("seg_start synced (dist check failed)");
-        // pixels with dist < 0 or >= D
-        return fail(H3D_EARG, "dist outside [0, %d)", D);
-      }
-    } else {
-      stamp("prep launched");
-    }
-  }
-
-  // 2. chunk table
-  stamp("seg_start synced");
-  std::vector<int64_t> cs;
-  std::vector<int32_t> cl, cd, scb(D), sce(D);
-  std::vector<SegState> st(S);
-  std::vector<int64_t> lpx(S);
-  int n_chunks = 0;
-  if (dev_tables) {
-    n_chunks = (int)std::min<int64_t>(n / kChunk + D + 1, INT32_MAX);  // an upper bound
-  } else {
-    for (int d = 0; d < D; ++d) {
-      scb[d] = (int32_t)cl.size();
-      for (int64_t a = seg_start[d]; a < seg_start[d + 1]; a += kChunk) {
-        cs.push_back(a);
-        cl.push_back((int32_t)std::min<int64_t>(kChunk, seg_start[d + 1] - a));
-        cd.push_back(d);
-      }
-      sce[d] = (int32_t)cl.size();
-    }
-    n_chunks = (int)cl.size();
-
-    // global pixel counts per segment (all ranks)
-    std::vector<double> cnt(S, 0.0);
-    for (int d = 0; d < D; ++d)
-      for (int c = 0; c < C; ++c) cnt[d * C + c] = (double)(seg_start[d + 1] - seg_start[d]);
-    double* d_cnt = (double*)scratch(ctx, "seg_cnt", S * 8);
-    if (!d_cnt) return fail(H3D_ENOMEM, "seg_cnt");
-    if (reduce) {
-      HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), S * 8, hipMemcpyHostToDevice, s));
-      if (reduce(d_cnt, S, user)) return fail(H3D_EHIP, "allreduce callback failed");
-      HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, S * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-    }
-    for (int sg = 0; sg < S; ++sg)
-      seg_init(&st[sg], (long long)cnt[sg], nrep[sg % C], ctx->qcml_tol);
-    for (int d = 0; d < D; ++d)
-      for (int c = 0; c < C; ++c) lpx[d * C + c] = seg_start[d + 1] - seg_start[d];
-  }
-
-  // the per-call tables go up as ONE copy from a pinned staging buffer (nine
-  // pageable copies cost ~0.3 ms of host-side gaps per cfg2 step: each
-  // staged and launched its own blit)
-  std::vector<int32_t> nrep32(nrep.begin(), nrep.end());
-  struct Part {
-    const void* src;
-    size_t bytes, off;
-  };
-  // (dev_tables: the chunk / segment tables are k_disp_tables' outputs, only
-  // their room is reserved and nothing of them is copied)
-  const size_t nch = (size_t)std::max(n_chunks, 1);
-  Part parts[] = {{cs.data(), nch * 8, 0},               {cl.data(), nch * 4, 0},
-                  {cd.data(), nch * 4, 0},               {scb.data(), (size_t)D * 4, 0},
-                  {sce.data(), (size_t)D * 4, 0},        {nrep32.data(), (size_t)C * 4, 0},
-                  {rep_idx.data(), rep_idx.size() * 4, 0},
-                  {st.data(), (size_t)S * sizeof(SegState), 0},
-                  {lpx.data(), (size_t)S * 8, 0}};
-  size_t blob = 0;
-  for (Part& q : parts) {
-    q.off = blob;
-    blob += (q.bytes + 255) & ~(size_t)255;
-  }
-  // the bytes that go up: everything, or (dev_tables) nrep + rep_idx only
-  const size_t up_lo = dev_tables ? parts[5].off : 0;
-  const size_t up_hi = dev_tables ? parts[7].off : blob;
-  if (!ctx->h_stage_done)
-    HIP_TRY(hipEventCreateWithFlags(&ctx->h_stage_done, hipEventDisableTiming));
-  else
-    HIP_TRY(hipEventSynchronize(ctx->h_stage_done));  // the previous copy has read it
-  if (ctx->h_stage_bytes < blob) {
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    ctx->h_stage = nullptr;
-    ctx->h_stage_bytes = 0;
-    HIP_TRY(hipHostMalloc(&ctx->h_stage, blob, hipHostMallocDefault));
-    ctx->h_stage_bytes = blob;
-  }
-  char* d_blob = (char*)scratch(ctx, "disp_tables", blob);
-  if (!d_blob) return fail(H3D_ENOMEM, "disp tables");
-  for (int qi = dev_tables ? 5 : 0; qi < (dev_tables ? 7 : 9); ++qi)
-    if (parts[qi].bytes)
-      std::memcpy((char*)ctx->h_stage + parts[qi].off, parts[qi].src, parts[qi].bytes);
-  HIP_TRY(hipMemcpyAsync(d_blob + up_lo, (char*)ctx->h_stage + up_lo, up_hi - up_lo,
-                         hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(ctx->h_stage_done, s));
-  int64_t* d_cs = (int64_t*)(d_blob + parts[0].off);
-  int32_t* d_cl = (int32_t*)(d_blob + parts[1].off);
-  int32_t* d_cd = (int32_t*)(d_blob + parts[2].off);
-  int32_t* d_scb = (int32_t*)(d_blob + parts[3].off);
-  int32_t* d_sce = (int32_t*)(d_blob + parts[4].off);
-  int32_t* d_nrep = (int32_t*)(d_blob + parts[5].off);
-  int32_t* d_repidx = (int32_t*)(d_blob + parts[6].off);
-  SegState* d_st = (SegState*)(d_blob + parts[7].off);
-  int64_t* d_lpx = (int64_t*)(d_blob + parts[8].off);
-  const size_t max_items = (size_t)std::max(n_chunks, 1) * C;
-  int32_t* d_list = (int32_t*)scratch(ctx, "work_list", max_items * 4);
-  // len, active, eq_len, live; k_disp_work's task heads (kTaskHeadStride apart)
-  int32_t* d_meta = (int32_t*)scratch(ctx, "work_meta", kWorkMetaInts * 4);
-  int32_t* d_slb = (int32_t*)scratch(ctx, "seg_lb", S * 4);
-  int32_t* d_sle = (int32_t*)scratch(ctx, "seg_le", S * 4);
-  double* d_partial = (double*)scratch(ctx, "partial", max_items * 8 * kWavesPerBlock);
-  double* d_total = (double*)scratch(ctx, "seg_total", S * 8);
-  int* d_flags = (int*)scratch(ctx, "seg_flags", S * 4);
-  double* d_res = (double*)scratch(ctx, "seg_result", S * 8);
-  if (!d_cs || !d_cl || !d_cd || !d_scb || !d_sce || !d_nrep || !d_repidx ||
-      !d_st || !d_lpx || !d_list || !d_meta || !d_slb || !d_sle || !d_partial ||
-      !d_total || !d_flags || !d_res)
-    return fail(H3D_ENOMEM, "disp scratch");
-  if (!dev_tables) HIP_TRY(hipMemsetAsync(d_flags, 0, S * 4, s));  // else k_disp_tables
-  int* d_bad = (int*)scratch(ctx, "dist_bad", 4);
-  if (!d_bad) return fail(H3D_ENOMEM, "dist_bad");
-  // (an M = 6 instantiation for cfg4's R_c = 6 measured equal to M = 8:
-  // 111.5 vs 110.5 ms equalize per step, profiles/r02/q2)
-  const int mslot = (maxnr <= 2 && ctx->disp_m2) ? 2
-                    : maxnr <= 4                  ? 4
-                    : maxnr <= 8                  ? 8
-                    : maxnr <= 16                 ? 16
-                                                  : 32;
-  // every condition has exactly mslot replicates: the kFull instantiations
-  // of the equalize pass and the Brent kernels (M = 2 only, see k_brent;
-  // H3D_NLL_FULL=0: never)
-  const bool nll_full =
-      ctx->nll_full && mslot == 2 &&
-      std::all_of(nrep.begin(), nrep.end(), [&](int r) { return r == mslot; });
-  // dev_tables, single rank: k_brent and k_brent_gang are both launched every
-  // qcml iteration and the DEVICE picks one by the live-segment count (one
-  // workgroup per segment while they fill the CUs, gangs for the tail
-  // iterations, whose few live segments left most CUs idle: cfg2's fourth
-  // iteration ran ~55 searches on 55 CUs for 0.36 ms); the gang task table
-  // comes from k_disp_tables
-  GangTables gang;
-  const bool dual = dev_tables && !reduce && ctx->brent_gang == 1;
-  if (dual) {
-    const int grc = mslot == 2    ? gang_setup_dev<2>(ctx, n, D, C, &gang)
-                    : mslot == 4  ? gang_setup_dev<4>(ctx, n, D, C, &gang)
-                    : mslot == 8  ? gang_setup_dev<8>(ctx, n, D, C, &gang)
-                    : mslot == 16 ? gang_setup_dev<16>(ctx, n, D, C, &gang)
-                                  : gang_setup_dev<32>(ctx, n, D, C, &gang);
-    if (grc) return grc;
-  }
-  if (dev_tables) {
-    const int64_t* d_seg0 = (const int64_t*)scratch(ctx, "seg_start", (D + 1) * 8);
-    hipLaunchKernelGGL(k_disp_tables, dim3(1), dim3(1024), 0, s, d_seg0, D, C, n, d_nrep,
-                       d_cs, d_cl, d_cd, d_scb, d_sce, d_st, d_lpx, d_bad,
-                       dual ? gang.P : (int64_t)1, dual ? gang.task_seg : nullptr,
-                       dual ? gang.task_g : nullptr, ctx->qcml_tol, dual ? gang.T : 0,
-                       d_flags, dual ? gang.abort : nullptr);
-    dbg_launch("k_disp_tables");
-  }
-  stamp("tables uploaded");
-
-  // the single-rank Brent kernels' work queues, zeroed by k_seg_update
-  int* d_queue = (int*)scratch(ctx, "brent_queue", 2 * sizeof(int));
-  if (!d_queue) return fail(H3D_ENOMEM, "brent queue");
-  // initial active list
-  hipLaunchKernelGGL(k_seg_update, dim3(1), dim3(1024), 0, s, d_st, d_total,
-                     d_flags, S, C, d_nrep, d_scb, d_sce, d_list, d_slb, d_sle,
-                     d_res, d_meta, 1, 0, d_lpx, ctx->work_count, d_queue,
-                     dual ? gang.P : (int64_t)1, dual ? gang.task_seg : nullptr,
-                     dual ? gang.task_g : nullptr);
-  if (!ctx->h_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_meta, 32, hipHostMallocDefault));
-  int32_t* h_meta = ctx->h_meta;
-  const size_t res_bytes = (size_t)S * 8 + (size_t)S * sizeof(SegState) + 8;
-  if (ctx->h_res_bytes < res_bytes) {
-    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    ctx->h_res = nullptr;
-    ctx->h_res_bytes = 0;
-    HIP_TRY(hipHostMalloc(&ctx->h_res, res_bytes, hipHostMallocDefault));
-    ctx->h_res_bytes = res_bytes;
-  }
-  double* h_resd = (double*)ctx->h_res;
-  SegState* h_sst = (SegState*)(h_resd + S);
-  int* h_bad = (int*)(h_sst + S);
-  *h_bad = 0;
-  bool have_res = false;  // the results of the final poll are in h_res
-  int rounds = 0, batch = 2, rc = 0;
-  if (!reduce) {
-    // Single rank: one equalize pass per qcml iteration over every segment
-    // that needs one, then k_brent runs each such segment's whole Brent
-    // search in-kernel, then k_seg_update rebuilds the equalize list. The
-    // host polls the live-segment count every `batch` iterations (an
-    // iteration with nothing to do costs three empty launches).
-    int64_t* d_seg = (int64_t*)scratch(ctx, "seg_start", (D + 1) * 8);
-    if (!d_seg) return fail(H3D_ENOMEM, "brent scratch");
-    if (n == 0) HIP_TRY(hipMemsetAsync(d_seg, 0, (D + 1) * 8, s));
-    // H3D_BRENT: 1 (default) = gang searches (k_brent_gang) when the
-    // segments are fewer than the CUs, 2 = always, 0 = one workgroup per
-    // segment (k_brent)
-    bool use_gang = ctx->brent_gang != 0 && n > 0 && !dev_tables;
-    bool dual_on = dual;
-    if (use_gang) {
-      int grc = mslot == 2   ? gang_setup<2>(ctx, seg_start, D, C, &gang)
-                : mslot == 4 ? gang_setup<4>(ctx, seg_start, D, C, &gang)
-                : mslot == 8 ? gang_setup<8>(ctx, seg_start, D, C, &gang)
-                : mslot == 16 ? gang_setup<16>(ctx, seg_start, D, C, &gang)
-                              : gang_setup<32>(ctx, seg_start, D, C, &gang);
-      if (grc == 1) use_gang = false;
-      else if (grc) return grc;
-    }
-    // first poll after 5 iterations (cfg2's searches end after 5; a poll is
-    // a host sync plus the relaunch latency, ~50 us of idle GPU -- r03 host
-    // stamps), then every 2
-    batch = 5;
-    while (true) {
-      for (int b = 0; b < batch; ++b) {
-#define H3D_QCML_ITER(MM, FF)                                                             \
-  launch_disp_work<MM, false, FF>(                                                        \
-      ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st,     \
-      d_flags, d_list, d_meta, d_partial);                                                \
-  dbg_launch("equalize");                                                                 \
-  if (dual_on) {                                                                          \
-    launch_brent<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res,  \
-                         d_queue, d_meta, ctx->n_cu, gang.abort, true);                    \
-    dbg_launch("k_brent (dual)");                                                         \
-    launch_brent_gang<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags,    \
-                              d_res, d_queue + 1, gang, d_meta, ctx->n_cu, true);         \
-    dbg_launch("k_brent_gang (dual)");                                                    \
-  } else if (use_gang)                                                                    \
-    launch_brent_gang<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags,    \
-                              d_res, d_queue + 1, gang, nullptr, 0, true);                \
-  else                                                                                    \
-    launch_brent<MM, FF>(ctx, pd, n, d_seg, S, C, d_repidx, d_nrep, d_st, d_flags, d_res,  \
-                         d_queue, nullptr, 0, nullptr, true)
-        dbg_launch("before qcml iteration");
-        if (mslot == 2 && nll_full) { H3D_QCML_ITER(2, true); }
-        else if (mslot == 2) { H3D_QCML_ITER(2, false); }
-        else if (mslot == 4) { H3D_QCML_ITER(4, false); }
-        else if (mslot == 8) { H3D_QCML_ITER(8, false); }
-        else if (mslot == 16) { H3D_QCML_ITER(16, false); }
-        else { H3D_QCML_ITER(32, false); }
-#undef H3D_QCML_ITER
-        {
-          ProfScope ps(ctx, "disp_update", 0);
-          hipLaunchKernelGGL(k_seg_update, dim3(1), dim3(1024), 0, s, d_st, d_total,
-                             d_flags, S, C, d_nrep, d_scb, d_sce, d_list, d_slb, d_sle,
-                             d_res, d_meta, 0, 0, d_lpx, ctx->work_count, d_queue,
-                             dual_on ? gang.P : (int64_t)1,
-                             dual_on ? gang.task_seg : nullptr,
-                             dual_on ? gang.task_g : nullptr);
-        }
-        ++rounds;
-      }
-      // the poll, and speculatively what follows a final one: the result
-      // copies (pinned) and the requested smoother behind them, so a final
-      // poll costs one host round trip (r03s trace: ~0.12 ms of host gaps
-      // after the fifth iteration); a poll that finds live segments simply
-      // runs them, and a later poll redoes both
-      hipEvent_t copied = ev_get(ctx);
-      if (hipMemcpyAsync(h_meta, d_meta, 16, hipMemcpyDeviceToHost, s) != hipSuccess ||
-          ((use_gang || dual_on) &&
-           hipMemcpyAsync(h_meta + 4, gang.abort, 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-          hipMemcpyAsync(h_resd, d_res, (size_t)S * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-          hipMemcpyAsync(h_sst, d_st, (size_t)S * sizeof(SegState), hipMemcpyDeviceToHost, s) !=
-              hipSuccess ||
-          (dev_tables && hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-          hipEventRecord(copied, s) != hipSuccess) {
-        ctx->event_pool.push_back(copied);
-        rc = fail(H3D_EHIP, "disp round copies failed: %s", hipGetErrorString(hipGetLastError()));
-        break;
-      }
-      // (speculatively only where the smoother is the device's, enqueued
-      // without a wait; the host smoother of D > kTableMaxD runs once, on
-      // the final result, below -- on an intermediate poll it would block
-      // and could reject a table that is not final)
-      if (treq && D <= kTableMaxD) {
-        rc = h3d_disp_tables_dev(ctx, d_res, D, C, treq->weighted, treq->frac, treq->aff,
-                                 treq->d_tables);
-        if (rc) {
-          (void)hipEventSynchronize(copied);
-          ctx->event_pool.push_back(copied);
-          break;
-        }
-      }
-      const hipError_t ce = hipEventSynchronize(copied);
-      ctx->event_pool.push_back(copied);
-      if (ce != hipSuccess) {
-        rc = fail(H3D_EHIP, "disp round sync failed: %s", hipGetErrorString(ce));
-        break;
-      }
-      have_res = true;
-      stamp("poll");
-      if (std::getenv("H3D_DEBUG"))
-        fprintf(stderr, "[h3d] qcml iterations=%d live_segments=%d gang=%d abort=%d\n",
-                rounds, h_meta[3], use_gang ? 1 : dual_on ? 2 : 0,
-                (use_gang || dual_on) ? h_meta[4] : 0);
-      if (dual_on && h_meta[4]) {
-        // a gang aborted: k_brent (gated on the same flag) already took over
-        // the following iterations on the device; launch it alone from here
-        dual_on = false;
-        ctx->gang_aborts += 1;
-      }
-      if (use_gang && h_meta[4]) {
-        // a gang's wait timed out (CUs held elsewhere): its segments stayed
-        // in kEqualize and repeat their iteration; finish with k_brent
-        use_gang = false;
-        ctx->gang_aborts += 1;
-        continue;
-      }
-      if (h_meta[3] == 0) break;
-      if (rounds > 2000) {
-        rc = fail(H3D_ENOCONV, "estimate_disp did not terminate");
-        break;
-      }
-      batch = 2;
-    }
-  }
-  while (reduce && !rc) {
-    for (int b = 0; b < batch; ++b) {
-      {
-        // every width the single-rank driver picks (mslot 2 fell through to
-        // the M = 32 instantiation here: 13.1 vs 5.5 ms of equalize per cfg2
-        // step, bench --noop-reduce)
-        switch (mslot) {
-          case 2:
-            launch_disp_work<2, true>(ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st, d_flags, d_list, d_meta, d_partial);
-            break;
-          case 4:
-            launch_disp_work<4, true>(ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st, d_flags, d_list, d_meta, d_partial);
-            break;
-          case 8:
-            launch_disp_work<8, true>(ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st, d_flags, d_list, d_meta, d_partial);
-            break;
-          case 16:
-            launch_disp_work<16, true>(ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st, d_flags, d_list, d_meta, d_partial);
-            break;
-          default:
-            launch_disp_work<32, true>(ctx, max_items, raw_s, f_s, pd, n, d_cs, d_cl, d_cd, C, d_repidx, d_nrep, d_st, d_flags, d_list, d_meta, d_partial);
-        }
-      }
-      {
-        ProfScope ps(ctx, "disp_reduce", 0);
-        // this rank's per-segment sums; the cross-rank all-reduce follows and
-        // k_seg_update steps the (identical) state machines
-        hipLaunchKernelGGL(k_seg_reduce, dim3((S + 3) / 4), dim3(256), 0, s,
-                           d_partial, d_slb, d_sle, S, d_total, nullptr, d_flags,
-                           d_nrep, C, d_res);
-      }
-      if (reduce(d_total, S, user)) {
-        rc = fail(H3D_EHIP, "allreduce callback failed");
-        break;
-      }
-      {
-        ProfScope ps(ctx, "disp_update", 0);
-        hipLaunchKernelGGL(k_seg_update, dim3(1), dim3(1024), 0, s, d_st, d_total,
-                           d_flags, S, C, d_nrep, d_scb, d_sce, d_list, d_slb,
-                           d_sle, d_res, d_meta, 0, 1, d_lpx, ctx->work_count, nullptr);
-      }
-      ++rounds;
-    }
-    if (rc) break;
-    if (hipMemcpyAsync(h_meta, d_meta, 16, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      rc = fail(H3D_EHIP, "disp round sync failed: %s", hipGetErrorString(hipGetLastError()));
-      break;
-    }
-    if (std::getenv("H3D_DEBUG"))
-      fprintf(stderr, "[h3d] disp rounds=%d active_items=%d live_segments=%d\n", rounds,
-              h_meta[1], h_meta[3]);
-    // terminate on the genome-wide live-segment count (identical on every
-    // rank), not on this rank's own work-list length: a rank without pixels
-    // in the still-active segments must keep joining the collective reduce
-    if (h_meta[3] == 0) break;
-    if (rounds > 200000) {
-      rc = fail(H3D_ENOCONV, "estimate_disp did not terminate");
-      break;
-    }
-    batch = std::min(batch * 2, 8);
-  }
-  if (rc) return rc;
-  // a launch error of the qcml loop is this call's, not a later call's
-  HIP_TRY(hipGetLastError());
-  std::vector<int32_t> fl(S);
-  if (!have_res) {
-    // (the multi-rank path) the results into the pinned zone; the smoother
-    // runs behind the copies, the host waits for the copies only
-    HIP_TRY(hipMemcpyAsync(h_resd, d_res, (size_t)S * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(h_sst, d_st, (size_t)S * sizeof(SegState), hipMemcpyDeviceToHost, s));
-    if (dev_tables) HIP_TRY(hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-    hipEvent_t copied = ev_get(ctx);
-    HIP_TRY(hipEventRecord(copied, s));
-    const int trc = treq ? h3d_disp_tables_dev(ctx, d_res, D, C, treq->weighted, treq->frac,
-                                               treq->aff, treq->d_tables)
-                         : 0;
-    const hipError_t e = hipEventSynchronize(copied);
-    ctx->event_pool.push_back(copied);
-    if (trc) return trc;
-    if (e != hipSuccess) return fail(H3D_EHIP, "result copy: %s", hipGetErrorString(e));
-  }
-  std::memcpy(disp_per_dist, h_resd, (size_t)S * 8);
-  std::memcpy(st.data(), h_sst, (size_t)S * sizeof(SegState));
-  ctx->last_S = S;
-  const int bad = dev_tables ? *h_bad : 0;
-  stamp("results");
-  if (bad) return fail(H3D_EARG, "dist outside [0, %d)", D);
-  int all = 0;
-  for (int sg = 0; sg < S; ++sg) {
-    fl[sg] = st[sg].flags;
-    all |= fl[sg];
-  }
-  if (seg_flags_out) std::memcpy(seg_flags_out, fl.data(), S * 4);
-  if (const int frc = flags_to_code(all)) return frc;
-  if (have_res && treq && D > kTableMaxD) {
-    // the host smoother (h3d_disp_tables_dev's D > kTableMaxD branch), once,
-    // on the final result
-    const int trc = h3d_disp_tables_dev(ctx, d_res, D, C, treq->weighted, treq->frac,
-                                        treq->aff, treq->d_tables);
-    if (trc) return trc;
-  }
-  return 0;
-}
-}  // namespace
 
 int h3d_disp_per_dist(h3d_ctx* ctx, const int64_t* raw, const double* f,
                       const int32_t* dist, int64_t n, int R, int C,
@@ -1472,11 +1416,10 @@ int h3d_cml(h3d_ctx* ctx, const double* data, int64_t n, int r, double* disp_out
   HIP_TRY(hipMemcpyAsync(d_nr, &nrep, 4, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_st, &st, sizeof(SegState), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(d_fl, 0, 4, s));
-  const int m = r <= 4 ? 4 : r <= 8 ? 8 : r <= 16 ? 16 : 32;
-  if (m == 4) launch_brent<4>(ctx, d_pd, n, d_seg, 1, 1, d_ri, d_nr, d_st, d_fl, d_res, d_q);
-  else if (m == 8) launch_brent<8>(ctx, d_pd, n, d_seg, 1, 1, d_ri, d_nr, d_st, d_fl, d_res, d_q);
-  else if (m == 16) launch_brent<16>(ctx, d_pd, n, d_seg, 1, 1, d_ri, d_nr, d_st, d_fl, d_res, d_q);
-  else launch_brent<32>(ctx, d_pd, n, d_seg, 1, 1, d_ri, d_nr, d_st, d_fl, d_res, d_q);
+  with_width(r <= 4 ? 4 : r <= 8 ? 8 : r <= 16 ? 16 : 32, false, [&](auto m, auto) {
+    launch_brent<decltype(m)::value>(ctx, d_pd, n, d_seg, 1, 1, d_ri, d_nr, d_st, d_fl, d_res,
+                                     d_q);
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof(SegState), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

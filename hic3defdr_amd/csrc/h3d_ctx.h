@@ -107,30 +107,11 @@ struct h3d_ctx {
   hipStream_t bounce_stream = nullptr;
   void* land = nullptr;
   size_t land_cap = 0;
-  // tuning knobs (env at h3d_open): H3D_DISP_W = min waves/SIMD of the
-  // disp_work register budget (1, 2, 3, 4); H3D_DISP_SORT = 0 (distance) or
-  // 1 (distance, total count)
-  int disp_w = 4;  // measured best (sweep at 7413b12, equalize ms/step for
-                   // W 1/2/3/4: 10.7 / 10.55 / 9.76 / 9.62)
-  // H3D_DISP_SORT: pixel order inside a distance segment. 0 position, 1
-  // (total count) -- r01: 55.6 -> 52.5 ms --, 2 one (max, min count) order
-  // per condition -- r02 cfg2: equalize 7.62 -> 5.68 ms, 277 -> 311 Mpx/s;
-  // cfg4 equalize 118 -> 111 ms (profiles/r02/sortab)
-  int disp_sort = 2;
-  int nll_w = 1;  // H3D_NLL_W: min waves/SIMD of the NLL-only pass (1, 2, 4)
-  // H3D_DISP_M2 / _W2: the M = 2 instantiation for R_c <= 2 and its
-  // equalize register budget. r02 cfg2 (10 steps, two runs): M = 4 305 / 316
-  // Mpx/s; M = 2 at W 4 / 5 / 6: 320 (327) / 317 / 307 -- the gain is
-  // k_brent<2> (3.5 vs 3.9 ms), equalize is unchanged (same VGPR profile)
-  int disp_w2 = 4;
+  // tuning knobs (env at h3d_open; the settled ones are listed in DESIGN.md,
+  // "Settled switches")
   // k_disp_work: eighths of the task rounds dealt statically (the rest from
   // a device counter); H3D_EQ_STATIC8
   int eq_static8 = 4;
-  // H3D_PACK_GATHER: a condition of <= 2 replicates gathers from a 32-byte
-  // packed copy of its replicates' (raw, f) written by the key pass (one
-  // sector per pixel instead of a raw and an f line)
-  int pack_gather = 1;
-  int disp_m2 = 1;
   // H3D_BRENT: 1 = gang Brent searches (k_brent_gang) where one workgroup
   // per segment leaves CUs idle, 2 = always, 0 = k_brent only
   int brent_gang = 1;
@@ -157,11 +138,6 @@ struct h3d_ctx {
   // (h3d_disp_seg_stats)
   int last_S = 0;
   h3dint::TablePending tab_pending;
-  // H3D_DEV_SEG_TABLES (default 1): estimate_disp's chunk / segment tables
-  // built on the device (k_disp_tables) where no gangs are needed
-  int dev_seg_tables = 1;
-  int disp_w8 = 4;  // H3D_DISP_W8: equalize register budget for M = 8
-                    // (cfg4 sweep r02, ms/step W 1/2/3/4: 214/214/199/197)
 };
 
 namespace h3dint {

@@ -80,43 +80,6 @@ struct SoaRows {
   double* f[kMaxReps];
 };
 
-// AoS (n, R) -> distance-sorted SoA rows
-static __global__ void k_gather_soa(const int32_t* __restrict__ perm,
-                                    const int32_t* __restrict__ raw,
-                                    const double* __restrict__ f, int64_t n, int R,
-                                    SoaRows dst) {
-  if (R == 4 && ((uintptr_t)raw & 15) == 0 && ((uintptr_t)f & 15) == 0) {
-    // the common shape: one 16 B load of the raw row, two 16 B loads of the
-    // f row per pixel (rows are 16 B aligned), so the random row gather
-    // issues 3 memory instructions per lane instead of 8
-    const int4* raw4 = reinterpret_cast<const int4*>(raw);
-    const double2* f2 = reinterpret_cast<const double2*>(f);
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t src = perm[i];
-      const int4 rv = raw4[src];
-      const double2 fa = f2[2 * src], fb = f2[2 * src + 1];
-      dst.raw[0][i] = rv.x;
-      dst.raw[1][i] = rv.y;
-      dst.raw[2][i] = rv.z;
-      dst.raw[3][i] = rv.w;
-      dst.f[0][i] = fa.x;
-      dst.f[1][i] = fa.y;
-      dst.f[2][i] = fb.x;
-      dst.f[3][i] = fb.y;
-    }
-    return;
-  }
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t src = perm[i];
-    for (int r = 0; r < R; ++r) {
-      dst.raw[r][i] = raw[src * R + r];
-      dst.f[r][i] = f[src * R + r];
-    }
-  }
-}
-
 // Gather of ONE condition's replicates through that condition's own pixel
 // order: dst row j (replicate reps[j]) = raw / f column reps[j] of the AoS
 // rows perm[i]. A workgroup takes kGatherTile output pixels, reads their
@@ -268,32 +231,6 @@ static __global__ void k_gather_pack2(const int32_t* __restrict__ perm,
       dst.raw[1][i] = rv.y;
       dst.f[1][i] = fv.y;
     }
-  }
-}
-
-// sort key (distance, total count capped to cbits bits): inside a distance
-// segment pixels of similar depth sit in the same wave, so the q2qnbinom
-// branches (tail side, series vs continued fraction) diverge less. The count
-// only orders pixels inside a segment (which segment a pixel joins is fixed
-// by the distance bits), so capping it changes no result beyond the order of
-// the segment's partial sums. K = uint32_t (16 count bits) whenever the
-// distance fits the other 16: fewer radix passes over half the key bytes.
-template <typename K>
-__global__ void k_dist_count_keys(const int32_t* __restrict__ dist,
-                                  const int32_t* __restrict__ raw, int64_t n,
-                                  int R, int cbits, K* __restrict__ keys) {
-  const uint64_t cap = (1ull << cbits) - 1ull;
-  // distances outside the key's range (incl. negative ones) saturate to the
-  // largest code, which is >= D: the caller's segment check rejects them
-  const uint64_t dcap = (uint64_t)(K)~(K)0 >> cbits;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t tot = 0;
-    for (int r = 0; r < R; ++r) tot += (uint32_t)raw[i * R + r];
-    if (tot > cap) tot = cap;
-    uint64_t d = (uint32_t)dist[i];
-    if (d > dcap) d = dcap;
-    keys[i] = (K)((d << cbits) | tot);
   }
 }
 

@@ -12,8 +12,8 @@
 #     -p  each run under rocprofv3 --kernel-trace --stats (kernel stats kept
 #         as gpurun_out/ab_<name>_kernel_stats.csv)
 # Examples: tools/ab_lib.sh "base:base: cur:cur:"
-#           tools/ab_lib.sh "w3::H3D_DISP_W=3 w4::H3D_DISP_W=4"
-#           tools/ab_lib.sh -c 4 "s2::H3D_DISP_SORT=2 s0::H3D_DISP_SORT=0"
+#           tools/ab_lib.sh "s4::H3D_EQ_STATIC8=4 s6::H3D_EQ_STATIC8=6"
+#           tools/ab_lib.sh -c 4 "lds128::H3D_BRENT_LDS_KB=128 lds0::H3D_BRENT_LDS_KB=0"
 set -e
 cfg=2; reps=2; steps=; tests=0; prof=0
 while getopts "c:r:s:tp" o; do
