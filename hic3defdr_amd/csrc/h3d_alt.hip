@@ -177,19 +177,6 @@ __global__ __launch_bounds__(kAltBlock) void k_mme_per_pixel(
 
 int alt_grid(h3d_ctx* ctx, int64_t n) { return grid_for(ctx, n, 16); }
 
-// raw int64 (caller's host array) -> device int32, rejecting counts the
-// int32 kernels cannot hold
-__global__ void k_i64_to_i32_alt(const int64_t* __restrict__ in,
-                                 int32_t* __restrict__ out, int64_t n,
-                                 int* __restrict__ overflow) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = in[i];
-    if (v < 0 || v > 0x7fffffffLL) atomicOr(overflow, 1);
-    out[i] = (int32_t)v;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -207,8 +194,9 @@ int h3d_lrt_poisson_dev(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
     return fail(H3D_EARG, "null device buffer");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int32_t* d_cond = (int32_t*)scratch(ctx, "cond_of_rep", R * 4);
-  if (!d_cond) return fail(H3D_ENOMEM, "poisson scratch");
+  Scratch sc{ctx};
+  int32_t* d_cond = sc.get<int32_t>("cond_of_rep", R);
+  if (!sc.ok) return fail(H3D_ENOMEM, "poisson scratch");
   HIP_TRY(hipMemcpyAsync(d_cond, cond_of_rep, R * 4, hipMemcpyHostToDevice, s));
   const int grid = alt_grid(ctx, n);
   const int m = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : 32;
@@ -237,23 +225,19 @@ int h3d_lrt_poisson(h3d_ctx* ctx, const int64_t* raw, const double* f,
   if (!raw || !f || !p || !llr || !mu0 || !mu1) return fail(H3D_EARG, "null buffer");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t* d_raw64 = (int64_t*)scratch(ctx, "in_raw64", n * R * 8);
-  int32_t* d_raw = (int32_t*)scratch(ctx, "in_raw", n * R * 4);
-  double* d_f = (double*)scratch(ctx, "in_f", n * R * 8);
-  double* d_out = (double*)scratch(ctx, "plrt_out", n * (3 + C) * 8);
-  int* d_ovf = (int*)scratch(ctx, "ovf", 4);
-  if (!d_raw64 || !d_raw || !d_f || !d_out || !d_ovf)
-    return fail(H3D_ENOMEM, "poisson inputs");
-  HIP_TRY(hipMemcpyAsync(d_raw64, raw, n * R * 8, hipMemcpyHostToDevice, s));
+  Scratch sc{ctx};
+  double* d_f = sc.get<double>("in_f", n * R);
+  double* d_out = sc.get<double>("plrt_out", n * (3 + C));
+  if (!sc.ok) return fail(H3D_ENOMEM, "poisson inputs");
+  int32_t* d_raw = nullptr;
+  int* d_ovf = nullptr;
+  if (int rc = upload_counts(ctx, raw, n * R, &d_raw, &d_ovf)) return rc;
   HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, s));
-  hipLaunchKernelGGL(k_i64_to_i32_alt, dim3(grid_for(ctx, n * R)), dim3(kAltBlock), 0,
-                     s, d_raw64, d_raw, n * R, d_ovf);
   double *dp = d_out, *dl = d_out + n, *dm0 = d_out + 2 * n, *dm1 = d_out + 3 * n;
   int rc = h3d_lrt_poisson_dev(ctx, d_raw, d_f, n, R, C, cond_of_rep, dp, dl, dm0, dm1);
   if (rc) return rc;
   int ovf = 0;
-  HIP_TRY(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, s));
+  if (int orc = counts_ovf_copy(ctx, d_ovf, &ovf)) return orc;
   HIP_TRY(hipMemcpyAsync(p, dp, n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(llr, dl, n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(mu0, dm0, n * 8, hipMemcpyDeviceToHost, s));
@@ -274,11 +258,12 @@ int h3d_mme_per_pixel(h3d_ctx* ctx, const double* data, const double* f,
   if (!data || !disp) return fail(H3D_EARG, "null buffer");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  double* d_data = (double*)scratch(ctx, "mme_in", n * R * 8);
-  double* d_f = f ? (double*)scratch(ctx, "mme_f", n * R * 8) : nullptr;
-  double* d_out = (double*)scratch(ctx, "mme_out", n * C * 8);
-  int32_t* d_cond = (int32_t*)scratch(ctx, "cond_of_rep", R * 4);
-  if (!d_data || (f && !d_f) || !d_out || !d_cond) return fail(H3D_ENOMEM, "mme scratch");
+  Scratch sc{ctx};
+  double* d_data = sc.get<double>("mme_in", n * R);
+  double* d_f = f ? sc.get<double>("mme_f", n * R) : nullptr;
+  double* d_out = sc.get<double>("mme_out", n * C);
+  int32_t* d_cond = sc.get<int32_t>("cond_of_rep", R);
+  if (!sc.ok) return fail(H3D_ENOMEM, "mme scratch");
   HIP_TRY(hipMemcpyAsync(d_data, data, n * R * 8, hipMemcpyHostToDevice, s));
   if (f) HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_cond, cond_of_rep, R * 4, hipMemcpyHostToDevice, s));

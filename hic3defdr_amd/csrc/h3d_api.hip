@@ -65,22 +65,17 @@ int h2d_pinned(h3d_ctx* ctx, void* d_dst, const void* src, size_t bytes, hipStre
   if (!ctx->bounce_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->bounce_ev, hipEventDisableTiming));
   // the buffer is rewritten only after every earlier copy out of it has
   // read it: wrap-around, growth and a change of stream wait on the last one
-  const bool wrap = ctx->bounce_off + need > ctx->bounce_cap;
+  const bool wrap = ctx->bounce_off + need > ctx->bounce.cap;
   if ((wrap || (ctx->bounce_stream && ctx->bounce_stream != s)) && ctx->bounce_stream) {
     HIP_TRY(hipEventSynchronize(ctx->bounce_ev));
     ctx->bounce_off = 0;
     ctx->bounce_stream = nullptr;
   }
-  if (need > ctx->bounce_cap) {
-    if (ctx->bounce) (void)hipHostFree(ctx->bounce);
-    ctx->bounce = nullptr;
-    ctx->bounce_cap = 0;
-    const size_t cap = std::max<size_t>(need, (size_t)1 << 20);
-    HIP_TRY(hipHostMalloc(&ctx->bounce, cap, hipHostMallocDefault));
-    ctx->bounce_cap = cap;
+  if (need > ctx->bounce.cap) {
+    if (int rc = ctx->bounce.grow(need, (size_t)1 << 20)) return rc;
     ctx->bounce_off = 0;
   }
-  char* b = (char*)ctx->bounce + ctx->bounce_off;
+  char* b = (char*)ctx->bounce.p + ctx->bounce_off;
   std::memcpy(b, src, bytes);
   HIP_TRY(hipMemcpyAsync(d_dst, b, bytes, hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(ctx->bounce_ev, s));
@@ -90,15 +85,31 @@ int h2d_pinned(h3d_ctx* ctx, void* d_dst, const void* src, size_t bytes, hipStre
 }
 
 void* pinned_rd(h3d_ctx* ctx, size_t bytes) {
-  if (bytes > ctx->land_cap) {
-    if (ctx->land) (void)hipHostFree(ctx->land);
-    ctx->land = nullptr;
-    ctx->land_cap = 0;
-    const size_t cap = std::max<size_t>(bytes, 4096);
-    if (hipHostMalloc(&ctx->land, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    ctx->land_cap = cap;
-  }
-  return ctx->land;
+  return ctx->land.grow(bytes, 4096) ? nullptr : ctx->land.p;
+}
+
+int counts_to_i32(h3d_ctx* ctx, const int64_t* d_raw64, int32_t* d_raw, int64_t count,
+                  int* d_ovf) {
+  HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, ctx->stream));
+  hipLaunchKernelGGL(k_i64_to_i32, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream,
+                     d_raw64, d_raw, count, d_ovf);
+  return 0;
+}
+
+int upload_counts(h3d_ctx* ctx, const int64_t* raw64, int64_t count, int32_t** d_raw,
+                  int** d_ovf) {
+  Scratch sc{ctx};
+  int64_t* d_raw64 = sc.get<int64_t>("in_raw64", count);
+  *d_raw = sc.get<int32_t>("in_raw", count);
+  *d_ovf = sc.get<int>("ovf", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "raw counts");
+  HIP_TRY(hipMemcpyAsync(d_raw64, raw64, count * 8, hipMemcpyHostToDevice, ctx->stream));
+  return counts_to_i32(ctx, d_raw64, *d_raw, count, *d_ovf);
+}
+
+int counts_ovf_copy(h3d_ctx* ctx, const int* d_ovf, int* h_ovf) {
+  HIP_TRY(hipMemcpyAsync(h_ovf, d_ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
 }
 
 int d2h_sync(h3d_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t s) {
@@ -309,6 +320,17 @@ long long gang_timeout(h3d_ctx* ctx) {
   return (long long)khz * 500;
 }
 
+// room for n_tasks tasks and the exchange of S segments in g->gmax slices
+int gang_buffers(h3d_ctx* ctx, GangTables* g, size_t n_tasks, int S) {
+  Scratch sc{ctx};
+  g->task_seg = sc.get<int32_t>("gang_seg", n_tasks);
+  g->task_g = sc.get<int32_t>("gang_g", n_tasks);
+  g->part = sc.get<double>("gang_part", (size_t)2 * S * g->gmax);
+  g->tag = sc.get<int>("gang_tag", (size_t)2 * S * g->gmax);
+  g->abort = sc.get<int>("gang_abort", 1);
+  return sc.ok ? 0 : fail(H3D_ENOMEM, "gang tables");
+}
+
 // The host-built gang tables (H3D_BRENT=2: every search in gangs). Returns 1
 // (nothing set up) when a gang would not fit the resident grid.
 template <int M>
@@ -339,13 +361,7 @@ int gang_setup(h3d_ctx* ctx, const std::vector<int64_t>& seg_start, int D, int C
   g->T = (int)ts.size();
   g->gmax = gmax;
   g->P = P;
-  g->task_seg = (int32_t*)scratch(ctx, "gang_seg", std::max<size_t>(1, ts.size()) * 4);
-  g->task_g = (int32_t*)scratch(ctx, "gang_g", std::max<size_t>(1, tg.size()) * 4);
-  g->part = (double*)scratch(ctx, "gang_part", (size_t)2 * S * gmax * 8);
-  g->tag = (int*)scratch(ctx, "gang_tag", (size_t)2 * S * gmax * 4);
-  g->abort = (int*)scratch(ctx, "gang_abort", 4);
-  if (!g->task_seg || !g->task_g || !g->part || !g->tag || !g->abort)
-    return fail(H3D_ENOMEM, "gang tables");
+  if (int rc = gang_buffers(ctx, g, std::max<size_t>(1, ts.size()), S)) return rc;
   if (g->T) {
     HIP_TRY(hipMemcpyAsync(g->task_seg, ts.data(), ts.size() * 4, hipMemcpyHostToDevice,
                            ctx->stream));
@@ -378,13 +394,7 @@ int gang_setup_dev(h3d_ctx* ctx, int64_t n, int D, int C, GangTables* g) {
   g->gmax = (int)std::max<int64_t>(1, (n + P - 1) / P);
   g->T = (int)std::min<int64_t>(INT32_MAX, (int64_t)C * (g->gmax + D));
   const int S = D * C;
-  g->task_seg = (int32_t*)scratch(ctx, "gang_seg", (size_t)g->T * 4);
-  g->task_g = (int32_t*)scratch(ctx, "gang_g", (size_t)g->T * 4);
-  g->part = (double*)scratch(ctx, "gang_part", (size_t)2 * S * g->gmax * 8);
-  g->tag = (int*)scratch(ctx, "gang_tag", (size_t)2 * S * g->gmax * 4);
-  g->abort = (int*)scratch(ctx, "gang_abort", 4);
-  if (!g->task_seg || !g->task_g || !g->part || !g->tag || !g->abort)
-    return fail(H3D_ENOMEM, "gang tables");
+  if (int rc = gang_buffers(ctx, g, (size_t)g->T, S)) return rc;
   // (task_seg's tail and abort are set by k_disp_tables, which fills the
   // table)
   g->timeout = gang_timeout(ctx);
@@ -529,32 +539,14 @@ void launch_disp_work(const DispCall& c) {
   }
 }
 
-// grow-only pinned host buffer of the ctx (freed by h3d_close: a per-call
-// hipHostFree would synchronise the device)
-int pinned_grow(void** buf, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return 0;
-  if (*buf) (void)hipHostFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  HIP_TRY(hipHostMalloc(buf, bytes, hipHostMallocDefault));
-  *cap = bytes;
-  return 0;
-}
-
 // stable radix sort of (key, value) pairs over key bits [begin_bit, end_bit)
 template <typename K>
 int radix_sort_pairs(h3d_ctx* ctx, const K* keys_in, K* keys_out, const int32_t* vals_in,
                      int32_t* vals_out, int64_t n, int begin_bit, int end_bit) {
-  size_t tmp_bytes = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in,
-                                             vals_out, (int)n, begin_bit, end_bit,
-                                             ctx->stream));
-  void* tmp = scratch(ctx, "cub_tmp", tmp_bytes);
-  if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_in, keys_out, vals_in,
-                                             vals_out, (int)n, begin_bit, end_bit,
-                                             ctx->stream));
-  return 0;
+  return cub_call(ctx, "cub_tmp", [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out,
+                                              (int)n, begin_bit, end_bit, ctx->stream);
+  });
 }
 
 int validate_and_plan(DispCall& c, const int32_t* cond_of_rep, int estimator) {
@@ -609,8 +601,9 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
   constexpr bool k32 = sizeof(K) == 4;
   const int cbits = k32 ? 16 : 64 - end_bit;
   const int sort_bits = k32 ? end_bit + 16 : 64;
-  int32_t* d_reps = (int32_t*)scratch(ctx, "sort_reps", (size_t)C * kMaxReps * 4);
-  if (!d_reps) return fail(H3D_ENOMEM, "sort buffers");
+  Scratch sc{ctx};
+  int32_t* d_reps = sc.get<int32_t>("sort_reps", (size_t)C * kMaxReps);
+  if (!sc.ok) return fail(H3D_ENOMEM, "sort buffers");
   if (int rc = h2d_pinned(ctx, d_reps, c.rep_idx.data(), (size_t)C * kMaxReps * 4, s)) return rc;
   // every condition of <= 2 replicates: one key pass for all of them, and
   // the gathers read its packed (raw, f) records -- one 32-byte sector per
@@ -619,14 +612,14 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
   int32_t* d_nrep = nullptr;
   CondPack2* packed = nullptr;
   if (pack) {
-    d_nrep = (int32_t*)scratch(ctx, "sort_nrep", (size_t)C * 4);
-    packed = (CondPack2*)scratch(ctx, "cond_pack2", (size_t)C * n * sizeof(CondPack2));
-    if (!d_nrep || !packed) return fail(H3D_ENOMEM, "packed gather rows");
+    d_nrep = sc.get<int32_t>("sort_nrep", (size_t)C);
+    packed = sc.get<CondPack2>("cond_pack2", (size_t)C * n);
+    if (!sc.ok) return fail(H3D_ENOMEM, "packed gather rows");
     if (int rc = h2d_pinned(ctx, d_nrep, c.nrep.data(), (size_t)C * 4, s)) return rc;
   }
-  K* keys = (K*)scratch(ctx, "dkeys", (pack ? (size_t)C : 1) * n * sizeof(K));
-  K* keys_s = (K*)scratch(ctx, "dkeys_s", n * sizeof(K));
-  if (!keys || !keys_s) return fail(H3D_ENOMEM, "sort keys");
+  K* keys = sc.template get<K>("dkeys", (pack ? (size_t)C : 1) * n);
+  K* keys_s = sc.template get<K>("dkeys_s", n);
+  if (!sc.ok) return fail(H3D_ENOMEM, "sort keys");
   for (int cc = 0; cc < C; ++cc) {
     const int32_t* reps_c = d_reps + cc * kMaxReps;
     K* keys_c = pack ? keys + (size_t)cc * n : keys;
@@ -668,15 +661,15 @@ int sort_and_gather(DispCall& c) {
   const int64_t n = c.n;
   const int R = c.R, D = c.D;
   ProfScope ps(ctx, "disp_prep", n);
-  int32_t* idx_in = (int32_t*)scratch(ctx, "idx_in", n * 4);
-  int32_t* idx_out = (int32_t*)scratch(ctx, "idx_out_c", n * 4);
-  c.dist_s = (int32_t*)scratch(ctx, "dist_s", n * 4);
-  c.raw_s = (int32_t*)scratch(ctx, "raw_s", n * R * 4);
-  c.f_s = (double*)scratch(ctx, "f_s", n * R * 8);
-  c.pd = (double*)scratch(ctx, "pd", n * R * 8);
-  c.d_seg = (int64_t*)scratch(ctx, "seg_start", (D + 1) * 8);
-  if (!idx_in || !idx_out || !c.dist_s || !c.raw_s || !c.f_s || !c.pd || !c.d_seg)
-    return fail(H3D_ENOMEM, "device allocation failed (n=%lld)", (long long)n);
+  Scratch sc{ctx};
+  int32_t* idx_in = sc.get<int32_t>("idx_in", n);
+  int32_t* idx_out = sc.get<int32_t>("idx_out_c", n);
+  c.dist_s = sc.get<int32_t>("dist_s", n);
+  c.raw_s = sc.get<int32_t>("raw_s", n * R);
+  c.f_s = sc.get<double>("f_s", n * R);
+  c.pd = sc.get<double>("pd", n * R);
+  c.d_seg = sc.get<int64_t>("seg_start", D + 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "device allocation failed (n=%lld)", (long long)n);
   hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, c.s, idx_in, n);
   int end_bit = 1;
   while ((1 << end_bit) <= D) ++end_bit;
@@ -731,8 +724,9 @@ int host_tables(DispCall& c, HostTables* t) {
   for (int d = 0; d < D; ++d)
     for (int cc = 0; cc < C; ++cc) t->lpx[d * C + cc] = seg_start[d + 1] - seg_start[d];
   std::vector<double> cnt(t->lpx.begin(), t->lpx.end());
-  double* d_cnt = (double*)scratch(ctx, "seg_cnt", S * 8);
-  if (!d_cnt) return fail(H3D_ENOMEM, "seg_cnt");
+  Scratch sc{ctx};
+  double* d_cnt = sc.get<double>("seg_cnt", S);
+  if (!sc.ok) return fail(H3D_ENOMEM, "seg_cnt");
   if (c.reduce) {
     HIP_TRY(hipMemcpyAsync(d_cnt, cnt.data(), S * 8, hipMemcpyHostToDevice, c.s));
     if (c.reduce(d_cnt, S, c.user)) return fail(H3D_EHIP, "allreduce callback failed");
@@ -789,13 +783,14 @@ int segment_tables(DispCall& c) {
     HIP_TRY(hipEventCreateWithFlags(&ctx->h_stage_done, hipEventDisableTiming));
   else
     HIP_TRY(hipEventSynchronize(ctx->h_stage_done));  // the previous copy has read it
-  if (int rc = pinned_grow(&ctx->h_stage, &ctx->h_stage_bytes, blob)) return rc;
-  char* d_blob = (char*)scratch(ctx, "disp_tables", blob);
-  if (!d_blob) return fail(H3D_ENOMEM, "disp tables");
+  if (int rc = ctx->h_stage.grow(blob)) return rc;
+  Scratch sc{ctx};
+  char* d_blob = sc.get<char>("disp_tables", blob);
+  if (!sc.ok) return fail(H3D_ENOMEM, "disp tables");
+  char* h_stage = (char*)ctx->h_stage.p;
   for (int qi = q_lo; qi < q_hi; ++qi)
-    if (parts[qi].bytes)
-      std::memcpy((char*)ctx->h_stage + parts[qi].off, parts[qi].src, parts[qi].bytes);
-  HIP_TRY(hipMemcpyAsync(d_blob + up_lo, (char*)ctx->h_stage + up_lo, up_hi - up_lo,
+    if (parts[qi].bytes) std::memcpy(h_stage + parts[qi].off, parts[qi].src, parts[qi].bytes);
+  HIP_TRY(hipMemcpyAsync(d_blob + up_lo, h_stage + up_lo, up_hi - up_lo,
                          hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(ctx->h_stage_done, s));
   c.d_cs = (int64_t*)(d_blob + parts[0].off);
@@ -808,19 +803,17 @@ int segment_tables(DispCall& c) {
   c.d_st = (SegState*)(d_blob + parts[7].off);
   c.d_lpx = (int64_t*)(d_blob + parts[8].off);
   c.max_items = nch * C;
-  c.d_list = (int32_t*)scratch(ctx, "work_list", c.max_items * 4);
+  c.d_list = sc.get<int32_t>("work_list", c.max_items);
   // len, active, eq_len, live; k_disp_work's task heads (kTaskHeadStride apart)
-  c.d_meta = (int32_t*)scratch(ctx, "work_meta", kWorkMetaInts * 4);
-  c.d_slb = (int32_t*)scratch(ctx, "seg_lb", S * 4);
-  c.d_sle = (int32_t*)scratch(ctx, "seg_le", S * 4);
-  c.d_partial = (double*)scratch(ctx, "partial", c.max_items * 8 * kWavesPerBlock);
-  c.d_total = (double*)scratch(ctx, "seg_total", S * 8);
-  c.d_flags = (int*)scratch(ctx, "seg_flags", S * 4);
-  c.d_res = (double*)scratch(ctx, "seg_result", S * 8);
-  c.d_bad = (int*)scratch(ctx, "dist_bad", 4);
-  if (!c.d_list || !c.d_meta || !c.d_slb || !c.d_sle || !c.d_partial || !c.d_total ||
-      !c.d_flags || !c.d_res || !c.d_bad)
-    return fail(H3D_ENOMEM, "disp scratch");
+  c.d_meta = sc.get<int32_t>("work_meta", kWorkMetaInts);
+  c.d_slb = sc.get<int32_t>("seg_lb", S);
+  c.d_sle = sc.get<int32_t>("seg_le", S);
+  c.d_partial = sc.get<double>("partial", c.max_items * kWavesPerBlock);
+  c.d_total = sc.get<double>("seg_total", S);
+  c.d_flags = sc.get<int>("seg_flags", S);
+  c.d_res = sc.get<double>("seg_result", S);
+  c.d_bad = sc.get<int>("dist_bad", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "disp scratch");
   if (!c.dev_tables) {
     HIP_TRY(hipMemsetAsync(c.d_flags, 0, S * 4, s));  // else k_disp_tables
   } else {
@@ -856,14 +849,15 @@ void launch_seg_update(DispCall& c, int init, int step) {
 // Stage: the first active list and the pinned zone the results land in.
 int start_qcml(DispCall& c) {
   h3d_ctx* ctx = c.ctx;
-  c.d_queue = (int*)scratch(ctx, "brent_queue", 2 * sizeof(int));
-  if (!c.d_queue) return fail(H3D_ENOMEM, "brent queue");
+  Scratch sc{ctx};
+  c.d_queue = sc.get<int>("brent_queue", 2);
+  if (!sc.ok) return fail(H3D_ENOMEM, "brent queue");
   launch_seg_update(c, 1, 0);
   if (!ctx->h_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_meta, 32, hipHostMallocDefault));
   c.h_meta = ctx->h_meta;
   const size_t res_bytes = (size_t)c.S * 8 + (size_t)c.S * sizeof(SegState) + 8;
-  if (int rc = pinned_grow(&ctx->h_res, &ctx->h_res_bytes, res_bytes)) return rc;
-  c.h_resd = (double*)ctx->h_res;
+  if (int rc = ctx->h_res.grow(res_bytes)) return rc;
+  c.h_resd = (double*)ctx->h_res.p;
   c.h_sst = (SegState*)(c.h_resd + c.S);
   c.h_bad = (int*)(c.h_sst + c.S);
   *c.h_bad = 0;
@@ -921,8 +915,9 @@ int poll_single_rank(DispCall& c, bool gangs) {
 int qcml_single_rank(DispCall& c) {
   h3d_ctx* ctx = c.ctx;
   if (c.n == 0) {
-    c.d_seg = (int64_t*)scratch(ctx, "seg_start", (c.D + 1) * 8);
-    if (!c.d_seg) return fail(H3D_ENOMEM, "brent scratch");
+    Scratch sc{ctx};
+    c.d_seg = sc.get<int64_t>("seg_start", c.D + 1);
+    if (!sc.ok) return fail(H3D_ENOMEM, "brent scratch");
     HIP_TRY(hipMemsetAsync(c.d_seg, 0, (c.D + 1) * 8, c.s));
   }
   // H3D_BRENT=2 (host-built tables): every search in gangs
@@ -1172,14 +1167,10 @@ void h3d_close(h3d_ctx* ctx) {
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
   if (ctx->work_count) (void)hipFree(ctx->work_count);
   if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
-  if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->h_stage_done) (void)hipEventDestroy(ctx->h_stage_done);
-  if (ctx->bounce) (void)hipHostFree(ctx->bounce);
   if (ctx->bounce_ev) (void)hipEventDestroy(ctx->bounce_ev);
-  if (ctx->land) (void)hipHostFree(ctx->land);
   if (ctx->own) (void)hipStreamDestroy(ctx->own);
-  delete ctx;
+  delete ctx;  // (the PinnedBufs free themselves)
 }
 
 int h3d_set_stream(h3d_ctx* ctx, void* stream) {
@@ -1293,20 +1284,16 @@ int h3d_disp_per_dist(h3d_ctx* ctx, const int64_t* raw, const double* f,
   double* d_f = nullptr;
   int32_t* d_dist = nullptr;
   if (n > 0) {
-    int64_t* d_raw64 = (int64_t*)scratch(ctx, "in_raw64", n * R * 8);
-    d_raw = (int32_t*)scratch(ctx, "in_raw", n * R * 4);
-    d_f = (double*)scratch(ctx, "in_f", n * R * 8);
-    d_dist = (int32_t*)scratch(ctx, "in_dist", n * 4);
-    int* d_ovf = (int*)scratch(ctx, "ovf", 4);
-    if (!d_raw64 || !d_raw || !d_f || !d_dist || !d_ovf) return fail(H3D_ENOMEM, "inputs");
-    HIP_TRY(hipMemcpyAsync(d_raw64, raw, n * R * 8, hipMemcpyHostToDevice, s));
+    Scratch sc{ctx};
+    d_f = sc.get<double>("in_f", n * R);
+    d_dist = sc.get<int32_t>("in_dist", n);
+    if (!sc.ok) return fail(H3D_ENOMEM, "inputs");
+    int* d_ovf = nullptr;
+    if (int rc = upload_counts(ctx, raw, n * R, &d_raw, &d_ovf)) return rc;
     HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_dist, dist, n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, s));
-    hipLaunchKernelGGL(k_i64_to_i32, dim3(grid_for(ctx, n * R)), dim3(kBlock), 0, s,
-                       d_raw64, d_raw, n * R, d_ovf);
     int ovf = 0;
-    HIP_TRY(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, s));
+    if (int rc = counts_ovf_copy(ctx, d_ovf, &ovf)) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     if (ovf) return fail(H3D_EINPUT, "raw counts must be in [0, 2^31)");
   }
@@ -1370,9 +1357,9 @@ int h3d_disp_tables(const double* disp_per_dist, int D, int C, int weighted,
 
 int h3d_disp_seg_stats(h3d_ctx* ctx, int S, int32_t* qiter, int32_t* evals) {
   if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (S != ctx->last_S || !ctx->h_res)
+  if (S != ctx->last_S || !ctx->h_res.p)
     return fail(H3D_EARG, "no estimate_disp result of %d segments (last: %d)", S, ctx->last_S);
-  const SegState* h_sst = (const SegState*)((const double*)ctx->h_res + S);
+  const SegState* h_sst = (const SegState*)((const double*)ctx->h_res.p + S);
   for (int s = 0; s < S; ++s) {
     if (qiter) qiter[s] = h_sst[s].qiter;
     if (evals) evals[s] = h_sst[s].evals;
@@ -1400,16 +1387,16 @@ int h3d_cml(h3d_ctx* ctx, const double* data, int64_t n, int r, double* disp_out
   for (int k = 0; k < kMaxReps; ++k) rep_idx[k] = k;
   const int64_t seg[2] = {0, n};
   const int32_t nrep = r;
-  double* d_pd = (double*)scratch(ctx, "cml_pd", (size_t)n * r * 8);
-  int64_t* d_seg = (int64_t*)scratch(ctx, "cml_seg", 16);
-  int32_t* d_ri = (int32_t*)scratch(ctx, "cml_ri", kMaxReps * 4);
-  int32_t* d_nr = (int32_t*)scratch(ctx, "cml_nr", 4);
-  SegState* d_st = (SegState*)scratch(ctx, "cml_st", sizeof(SegState));
-  int* d_fl = (int*)scratch(ctx, "cml_fl", 4);
-  double* d_res = (double*)scratch(ctx, "cml_res", 8);
-  int* d_q = (int*)scratch(ctx, "cml_queue", 4);
-  if (!d_pd || !d_seg || !d_ri || !d_nr || !d_st || !d_fl || !d_res || !d_q)
-    return fail(H3D_ENOMEM, "cml scratch");
+  Scratch sc{ctx};
+  double* d_pd = sc.get<double>("cml_pd", (size_t)n * r);
+  int64_t* d_seg = sc.get<int64_t>("cml_seg", 2);
+  int32_t* d_ri = sc.get<int32_t>("cml_ri", kMaxReps);
+  int32_t* d_nr = sc.get<int32_t>("cml_nr", 1);
+  SegState* d_st = sc.get<SegState>("cml_st", 1);
+  int* d_fl = sc.get<int>("cml_fl", 1);
+  double* d_res = sc.get<double>("cml_res", 1);
+  int* d_q = sc.get<int>("cml_queue", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "cml scratch");
   HIP_TRY(hipMemcpyAsync(d_pd, soa.data(), soa.size() * 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_seg, seg, 16, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_ri, rep_idx.data(), kMaxReps * 4, hipMemcpyHostToDevice, s));

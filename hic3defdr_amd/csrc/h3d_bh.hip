@@ -133,33 +133,43 @@ int h3d_bh_dev(h3d_ctx* ctx, const double* d_p, int64_t n, double* d_q) {
   if (n >= ((int64_t)1 << 31)) return fail(H3D_EARG, "n too large (%lld)", (long long)n);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  double* key = (double*)scratch(ctx, "bh_key", n * 8);
-  double* key_s = (double*)scratch(ctx, "bh_key_s", n * 8);
-  int32_t* idx = (int32_t*)scratch(ctx, "bh_idx", n * 4);
-  int32_t* idx_s = (int32_t*)scratch(ctx, "bh_idx_s", n * 4);
-  int32_t* fin = (int32_t*)scratch(ctx, "bh_fin", n * 4);
-  int32_t* d_m = (int32_t*)scratch(ctx, "bh_m", 4);
-  if (!key || !key_s || !idx || !idx_s || !fin || !d_m) return fail(H3D_ENOMEM, "bh scratch");
+  Scratch sc{ctx};
+  double* key = sc.get<double>("bh_key", n);
+  double* key_s = sc.get<double>("bh_key_s", n);
+  int32_t* idx = sc.get<int32_t>("bh_idx", n);
+  int32_t* idx_s = sc.get<int32_t>("bh_idx_s", n);
+  int32_t* fin = sc.get<int32_t>("bh_fin", n);
+  int32_t* d_m = sc.get<int32_t>("bh_m", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh scratch");
   ProfScope ps(ctx, "bh", n, 1);
   const int grid = grid_for(ctx, n);
   hipLaunchKernelGGL(k_bh_keys, dim3(grid), dim3(kBhBlock), 0, s, d_p, n, key, idx, fin);
-  size_t tb = 0, tb2 = 0, tb3 = 0;
-  HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, fin, d_m, (int)n, s));
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, key, key_s, idx, idx_s, (int)n, 0,
-                                             64, s));
   // the ratios reuse `key` (SortPairs leaves its input unread afterwards)
-  double* scanned = (double*)scratch(ctx, "bh_scan", n * 8);
-  if (!scanned) return fail(H3D_ENOMEM, "bh scratch");
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tb3, key, scanned, MinOp(), (int)n, s));
-  void* tmp = scratch(ctx, "cub_tmp_bh", std::max(tb, std::max(tb2, tb3)));
-  if (!tmp) return fail(H3D_ENOMEM, "bh scratch");
-  HIP_TRY(hipcub::DeviceReduce::Sum(tmp, tb, fin, d_m, (int)n, s));
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, key, key_s, idx, idx_s, (int)n, 0, 64,
-                                             s));
-  hipLaunchKernelGGL(k_bh_ratio, dim3(grid), dim3(kBhBlock), 0, s, key_s, d_m, key);
+  double* scanned = sc.get<double>("bh_scan", n);
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh scratch");
+  auto count = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceReduce::Sum(tmp, bytes, fin, d_m, (int)n, s);
+  };
+  auto sort = [&](void* tmp, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key_s, idx, idx_s, (int)n, 0, 64, s);
+  };
   // min-scan over the first m entries: the count lives on the device, so scan
   // all n -- entries >= m are never read (k_bh_scatter reads m - 1 - j < m)
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp, tb3, key, scanned, MinOp(), (int)n, s));
+  auto min_scan = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::InclusiveScan(tmp, bytes, key, scanned, MinOp(), (int)n, s);
+  };
+  // one temp for the three, reserved at the largest before the first runs
+  // (growing it between them would put a hipFree, a device synchronisation,
+  // between enqueued operations)
+  size_t tb = 0, tb2 = 0, tb3 = 0;
+  if (cub_bytes(count, &tb) || cub_bytes(sort, &tb2) || cub_bytes(min_scan, &tb3))
+    return H3D_EHIP;
+  sc.get<char>("cub_tmp_bh", std::max(tb, std::max(tb2, tb3)));
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh scratch");
+  if (int rc = cub_call(ctx, "cub_tmp_bh", count)) return rc;
+  if (int rc = cub_call(ctx, "cub_tmp_bh", sort)) return rc;
+  hipLaunchKernelGGL(k_bh_ratio, dim3(grid), dim3(kBhBlock), 0, s, key_s, d_m, key);
+  if (int rc = cub_call(ctx, "cub_tmp_bh", min_scan)) return rc;
   hipLaunchKernelGGL(k_bh_scatter, dim3(grid), dim3(kBhBlock), 0, s, scanned, idx_s, d_m, n,
                      d_q);
   HIP_TRY(hipGetLastError());
@@ -176,24 +186,30 @@ int h3d_bh_sort_dev(h3d_ctx* ctx, const double* d_p, const int64_t* d_val, int64
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  double* key = (double*)scratch(ctx, "bhs_key", n * 8);
-  int64_t* val = (int64_t*)scratch(ctx, "bhs_val", n * 8);
-  int32_t* fin = (int32_t*)scratch(ctx, "bhs_fin", n * 4);
-  int32_t* d_m = (int32_t*)scratch(ctx, "bhs_m", 4);
-  if (!key || !val || !fin || !d_m) return fail(H3D_ENOMEM, "bh sort scratch");
+  Scratch sc{ctx};
+  double* key = sc.get<double>("bhs_key", n);
+  int64_t* val = sc.get<int64_t>("bhs_val", n);
+  int32_t* fin = sc.get<int32_t>("bhs_fin", n);
+  int32_t* d_m = sc.get<int32_t>("bhs_m", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh sort scratch");
   ProfScope ps(ctx, "bh", n, 1);
   const int grid = grid_for(ctx, n);
   hipLaunchKernelGGL(k_bh_sort_in, dim3(grid), dim3(kBhBlock), 0, s, d_p, d_val, n, key, val,
                      fin);
+  auto count = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceReduce::Sum(tmp, bytes, fin, d_m, (int)n, s);
+  };
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, d_key_out, val, d_val_out,
+                                              (int)n, 0, 64, s);
+  };
+  // one temp for both, reserved at the larger before the first runs
   size_t tb = 0, tb2 = 0;
-  HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, fin, d_m, (int)n, s));
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, key, d_key_out, val, d_val_out,
-                                             (int)n, 0, 64, s));
-  void* tmp = scratch(ctx, "cub_tmp_bhs", std::max(tb, tb2));
-  if (!tmp) return fail(H3D_ENOMEM, "bh sort scratch");
-  HIP_TRY(hipcub::DeviceReduce::Sum(tmp, tb, fin, d_m, (int)n, s));
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb2, key, d_key_out, val, d_val_out, (int)n,
-                                             0, 64, s));
+  if (cub_bytes(count, &tb) || cub_bytes(sort, &tb2)) return H3D_EHIP;
+  sc.get<char>("cub_tmp_bhs", std::max(tb, tb2));
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh sort scratch");
+  if (int rc = cub_call(ctx, "cub_tmp_bhs", count)) return rc;
+  if (int rc = cub_call(ctx, "cub_tmp_bhs", sort)) return rc;
   HIP_TRY(hipGetLastError());
   if (m_finite) {
     int32_t hm = 0;
@@ -214,18 +230,18 @@ int h3d_bh_scan_dev(h3d_ctx* ctx, const double* d_ps, int64_t mb, int64_t offset
   if (mb >= ((int64_t)1 << 31)) return fail(H3D_EARG, "bucket too large (%lld)", (long long)mb);
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  double* rev = (double*)scratch(ctx, "bhs_rev", mb * 8);
-  double* srev = (double*)scratch(ctx, "bhs_srev", mb * 8);
-  if (!rev || !srev) return fail(H3D_ENOMEM, "bh scan scratch");
+  Scratch sc{ctx};
+  double* rev = sc.get<double>("bhs_rev", mb);
+  double* srev = sc.get<double>("bhs_srev", mb);
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh scan scratch");
   ProfScope ps(ctx, "bh", mb, 1);
   const int grid = grid_for(ctx, mb);
   hipLaunchKernelGGL(k_bh_ratio_off, dim3(grid), dim3(kBhBlock), 0, s, d_ps, mb, offset, m,
                      rev);
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tb, rev, srev, MinOp(), (int)mb, s));
-  void* tmp = scratch(ctx, "cub_tmp_bhs2", tb);
-  if (!tmp) return fail(H3D_ENOMEM, "bh scan scratch");
-  HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp, tb, rev, srev, MinOp(), (int)mb, s));
+  if (int rc = cub_call(ctx, "cub_tmp_bhs2", [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceScan::InclusiveScan(tmp, bytes, rev, srev, MinOp(), (int)mb, s);
+      }))
+    return rc;
   hipLaunchKernelGGL(k_bh_unreverse, dim3(grid), dim3(kBhBlock), 0, s, srev, mb, d_scanned);
   HIP_TRY(hipGetLastError());
   if (bucket_min) {
@@ -256,9 +272,10 @@ int h3d_bh_ctx(h3d_ctx* ctx, const double* p, int64_t n, double* q) {
   if (n < 0 || !p || !q) return fail(H3D_EARG, "null argument");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  double* d_p = (double*)scratch(ctx, "bh_in", n * 8);
-  double* d_q = (double*)scratch(ctx, "bh_out", n * 8);
-  if (!d_p || !d_q) return fail(H3D_ENOMEM, "bh buffers");
+  Scratch sc{ctx};
+  double* d_p = sc.get<double>("bh_in", n);
+  double* d_q = sc.get<double>("bh_out", n);
+  if (!sc.ok) return fail(H3D_ENOMEM, "bh buffers");
   HIP_TRY(hipMemcpyAsync(d_p, p, n * 8, hipMemcpyHostToDevice, s));
   if (int rc = h3d_bh_dev(ctx, d_p, n, d_q)) return rc;
   HIP_TRY(hipMemcpyAsync(q, d_q, n * 8, hipMemcpyDeviceToHost, s));

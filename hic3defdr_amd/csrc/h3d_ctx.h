@@ -59,6 +59,31 @@ struct TablePending {
   int active = 0, on_host = 0;
 };
 
+// grow-only pinned host buffer of the ctx, freed with it (a per-call
+// hipHostFree would synchronise the device)
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  // room for `bytes`: a smaller block is freed first and replaced by one of
+  // max(bytes, min_cap) -- its contents are not kept
+  int grow(size_t bytes, size_t min_cap = 0) {
+    if (cap >= bytes) return 0;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = bytes > min_cap ? bytes : min_cap;
+    HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+    cap = want;
+    return 0;
+  }
+};
+
 }  // namespace h3dint
 
 struct h3d_ctx {
@@ -85,13 +110,11 @@ struct h3d_ctx {
   // ctx's lifetime (a per-call hipHostFree would synchronise the device)
   int32_t* h_meta = nullptr;
   // pinned staging of estimate_disp's per-call tables (one H2D copy)
-  void* h_stage = nullptr;
-  size_t h_stage_bytes = 0;
+  h3dint::PinnedBuf h_stage;
   // pinned landing zone of estimate_disp's results (per-segment dispersion,
   // state, the distance check): pageable device-to-host copies blocked the
   // host one after another at the end of every call
-  void* h_res = nullptr;
-  size_t h_res_bytes = 0;
+  h3dint::PinnedBuf h_res;
   // recorded after each H2D copy out of h_stage: the next call waits on it
   // before rewriting (or freeing) the buffer, whichever way the last call
   // returned
@@ -101,12 +124,11 @@ struct h3d_ctx {
   // is staged by the HIP runtime behind every other pageable copy in flight
   // -- e.g. the class's background result copies -- and a 4-byte flag read
   // waited tens of ms behind them (r06an)
-  void* bounce = nullptr;
-  size_t bounce_cap = 0, bounce_off = 0;
+  h3dint::PinnedBuf bounce;
+  size_t bounce_off = 0;
   hipEvent_t bounce_ev = nullptr;
   hipStream_t bounce_stream = nullptr;
-  void* land = nullptr;
-  size_t land_cap = 0;
+  h3dint::PinnedBuf land;
   // tuning knobs (env at h3d_open; the settled ones are listed in DESIGN.md,
   // "Settled switches")
   // k_disp_work: eighths of the task rounds dealt statically (the rest from
@@ -152,6 +174,60 @@ void* scratch(h3d_ctx* ctx, const char* slot, size_t bytes);
 // the same, but a grown buffer keeps its first `keep` bytes (stream-ordered
 // copy; growth at least doubles the capacity)
 void* scratch_keep(h3d_ctx* ctx, const char* slot, size_t bytes, size_t keep);
+
+// a call's device buffers out of the ctx's slots, counted in elements; `ok`
+// turns false at the first failed allocation, so a group of buffers is
+// checked once: if (!sc.ok) return fail(H3D_ENOMEM, ...)
+struct Scratch {
+  h3d_ctx* ctx;
+  bool ok = true;
+  template <typename T>
+  T* get(const char* slot, size_t count) {
+    T* p = (T*)scratch(ctx, slot, count * sizeof(T));
+    ok = ok && p;
+    return p;
+  }
+  // scratch_keep: a grown buffer keeps its first keep_count elements
+  template <typename T>
+  T* keep(const char* slot, size_t count, size_t keep_count) {
+    T* p = (T*)scratch_keep(ctx, slot, count * sizeof(T), keep_count * sizeof(T));
+    ok = ok && p;
+    return p;
+  }
+};
+
+// hipcub's two-phase calls. op(tmp, bytes) is the hipcub call itself
+// (hipError_t(void*, size_t&)): with tmp = nullptr it only reports its temp
+// size. cub_bytes is that query alone; cub_call queries, takes the temp out
+// of the ctx slot (grow-only: a slot reserved larger beforehand is reused as
+// it is) and runs the operation.
+template <typename Op>
+int cub_bytes(Op op, size_t* bytes) {
+  *bytes = 0;
+  HIP_TRY(op(nullptr, *bytes));
+  return 0;
+}
+template <typename Op>
+int cub_call(h3d_ctx* ctx, const char* tmp_slot, Op op) {
+  size_t bytes = 0;
+  if (int rc = cub_bytes(op, &bytes)) return rc;
+  void* tmp = scratch(ctx, tmp_slot, bytes);
+  if (!tmp) return h3derr::fail(H3D_ENOMEM, "hipcub temp (%s, %zu bytes)", tmp_slot, bytes);
+  HIP_TRY(op(tmp, bytes));
+  return 0;
+}
+
+// Raw counts arrive as int64 and every kernel reads int32. counts_to_i32
+// (enqueued on the ctx stream) clears *d_ovf and converts `count` device
+// values, setting *d_ovf where one is outside [0, 2^31); upload_counts does
+// so for a host array, through the slots "in_raw64" / "in_raw" / "ovf";
+// counts_ovf_copy enqueues the word's copy into *h_ovf, which the caller
+// tests after its next stream synchronisation (H3D_EINPUT).
+int counts_to_i32(h3d_ctx* ctx, const int64_t* d_raw64, int32_t* d_raw, int64_t count,
+                  int* d_ovf);
+int upload_counts(h3d_ctx* ctx, const int64_t* raw64, int64_t count, int32_t** d_raw,
+                  int** d_ovf);
+int counts_ovf_copy(h3d_ctx* ctx, const int* d_ovf, int* h_ovf);
 hipEvent_t ev_get(h3d_ctx* ctx);
 // host -> device copy of `bytes` through the ctx's pinned bounce buffer,
 // stream-ordered on s (the source may be reused at once)

@@ -72,11 +72,11 @@ int lrt_run(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
   // d_dist == NULL: disp_table holds per-pixel dispersions (n, C), or with
   // `wide` per pixel and replicate (n, R)
   const size_t tab_n = d_dist ? (size_t)D * C : (size_t)n * (wide ? R : C);
-  double* d_tab = table_on_dev ? (double*)disp_table
-                               : (double*)scratch(ctx, "disp_table", tab_n * 8);
-  int32_t* d_cond = (int32_t*)scratch(ctx, "cond_of_rep", R * 4);
-  int* d_fl = (int*)scratch(ctx, "lrt_flags", 4);
-  if (!d_tab || !d_cond || !d_fl) return fail(H3D_ENOMEM, "lrt scratch");
+  Scratch sc{ctx};
+  double* d_tab = table_on_dev ? (double*)disp_table : sc.get<double>("disp_table", tab_n);
+  int32_t* d_cond = sc.get<int32_t>("cond_of_rep", R);
+  int* d_fl = sc.get<int>("lrt_flags", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "lrt scratch");
   if (!table_on_dev)
     HIP_TRY(hipMemcpyAsync(d_tab, disp_table, tab_n * 8, hipMemcpyHostToDevice, s));
   if (int rc = h2d_pinned(ctx, d_cond, cond_of_rep, R * 4, s)) return rc;
@@ -132,26 +132,22 @@ int lrt_host(h3d_ctx* ctx, const int64_t* raw, const double* f, const int32_t* d
   if (!raw || !f || !p || !llr || !mu0 || !mu1) return fail(H3D_EARG, "null buffer");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t* d_raw64 = (int64_t*)scratch(ctx, "in_raw64", n * R * 8);
-  int32_t* d_raw = (int32_t*)scratch(ctx, "in_raw", n * R * 4);
-  double* d_f = (double*)scratch(ctx, "in_f", n * R * 8);
-  int32_t* d_dist = dist ? (int32_t*)scratch(ctx, "in_dist", n * 4) : nullptr;
-  double* d_out = (double*)scratch(ctx, "lrt_out", n * (3 + 2 * C) * 8);
-  int* d_ovf = (int*)scratch(ctx, "ovf", 4);
-  if (!d_raw64 || !d_raw || !d_f || (dist && !d_dist) || !d_out || !d_ovf)
-    return fail(H3D_ENOMEM, "lrt inputs");
-  HIP_TRY(hipMemcpyAsync(d_raw64, raw, n * R * 8, hipMemcpyHostToDevice, s));
+  Scratch sc{ctx};
+  double* d_f = sc.get<double>("in_f", n * R);
+  int32_t* d_dist = dist ? sc.get<int32_t>("in_dist", n) : nullptr;
+  double* d_out = sc.get<double>("lrt_out", n * (3 + 2 * C));
+  if (!sc.ok) return fail(H3D_ENOMEM, "lrt inputs");
+  int32_t* d_raw = nullptr;
+  int* d_ovf = nullptr;
+  if (int rc = upload_counts(ctx, raw, n * R, &d_raw, &d_ovf)) return rc;
   HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
   if (dist) HIP_TRY(hipMemcpyAsync(d_dist, dist, n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, s));
-  hipLaunchKernelGGL(k_i64_to_i32, dim3(grid_for(ctx, n * R)), dim3(kBlock), 0, s,
-                     d_raw64, d_raw, n * R, d_ovf);
   double *dp = d_out, *dl = d_out + n, *dm0 = d_out + 2 * n, *dm1 = d_out + 3 * n,
          *dd = d_out + (3 + C) * n;
   int rc = lrt_run(ctx, d_raw, d_f, d_dist, disp_table, n, R, C, cond_of_rep, D,
                    refit_mu, dp, dl, dm0, dm1, disp_out ? dd : nullptr, wide);
   int ovf = 0;
-  HIP_TRY(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, s));
+  if (int orc = counts_ovf_copy(ctx, d_ovf, &ovf)) return orc;
   HIP_TRY(hipMemcpyAsync(p, dp, n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(llr, dl, n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(mu0, dm0, n * 8, hipMemcpyDeviceToHost, s));

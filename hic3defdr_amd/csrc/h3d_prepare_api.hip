@@ -19,138 +19,190 @@ using namespace h3d;
 using namespace h3dint;
 using h3derr::fail;
 
+namespace {
+
+// h3d_union_count reads as its stages; what they share travels in a
+// UnionCall, their results in ctx->prep (for h3d_union_fill).
+struct UnionCall {
+  h3d_ctx* ctx;  // the request
+  int R, n_bins;
+  const int64_t* const* indptr;
+  const int32_t* const* indices;
+  const double* const* data;
+  const int64_t* nnz;
+  const double* bias;
+  int dist_max;
+  hipStream_t s = nullptr;
+  int64_t sentinel = 0;  // n_bins^2: above every pixel's key
+  int end_bit = 1;       // the keys' bits
+  // one replicate's staging (reused by the next)
+  int64_t* d_indptr = nullptr;
+  int32_t *d_row = nullptr, *d_col = nullptr, *d_flag = nullptr, *d_pos = nullptr;
+  double* d_val = nullptr;
+  // the in-band entries of the replicates staged so far; the heads of their runs
+  int64_t tot = 0;
+  int64_t* d_keys = nullptr;
+  int32_t *d_ent = nullptr, *d_head = nullptr;
+};
+
+// Stage: the argument checks, and the staging buffers with the bias in them.
+// Only the in-band entries reach the per-entry key / sort / scan buffers, so
+// their size and the 2^31 cap follow the band, not the whole-chromosome nnz.
+int union_check_and_staging(UnionCall& u) {
+  h3d_ctx* ctx = u.ctx;
+  const int R = u.R, n_bins = u.n_bins;
+  if (!ctx || !u.indptr || !u.indices || !u.data || !u.nnz || !u.bias)
+    return fail(H3D_EARG, "null argument");
+  if (R < 1 || R > kMaxReps || n_bins < 1 || u.dist_max < 0)
+    return fail(H3D_EARG, "R=%d n_bins=%d dist_max=%d", R, n_bins, u.dist_max);
+  HIP_TRY(hipSetDevice(ctx->device));
+  u.s = ctx->stream;
+  ctx->prep = PrepUnion();
+  ctx->prep.R = R;
+  ctx->prep.n_bins = n_bins;
+  int64_t max_m = 0;
+  for (int r = 0; r < R; ++r) {
+    const int64_t m = u.nnz[r];
+    if (m < 0 || (m > 0 && (!u.indices[r] || !u.data[r])) || !u.indptr[r])
+      return fail(H3D_EARG, "replicate %d CSR", r);
+    if (u.indptr[r][n_bins] != m) return fail(H3D_EARG, "replicate %d indptr[-1] != nnz", r);
+    if (m >= ((int64_t)1 << 31)) return fail(H3D_EARG, "replicate %d: too many entries", r);
+    max_m = std::max(max_m, m);
+  }
+  u.sentinel = (int64_t)n_bins * n_bins;
+  while (u.end_bit < 63 && (((int64_t)1) << u.end_bit) <= u.sentinel) ++u.end_bit;
+  const size_t mm = (size_t)std::max<int64_t>(max_m, 1);
+  Scratch sc{ctx};
+  ctx->prep.bias = sc.get<double>("u_bias", (size_t)n_bins * R);
+  u.d_indptr = sc.get<int64_t>("u_indptr", (size_t)(n_bins + 1));
+  u.d_row = sc.get<int32_t>("u_row_of", mm);
+  u.d_col = sc.get<int32_t>("u_col", mm);
+  u.d_val = sc.get<double>("u_val_in", mm);
+  u.d_flag = sc.get<int32_t>("u_flag", mm);
+  u.d_pos = sc.get<int32_t>("u_pos", mm);
+  sc.get<int32_t>("u_cnt", 1);  // (no reader; the ctx goes on holding what it held)
+  if (!sc.ok) return fail(H3D_ENOMEM, "union staging");
+  return h2d_pinned(ctx, ctx->prep.bias, u.bias, (size_t)n_bins * R * 8, u.s);
+}
+
+// Stage: replicate r's m > 0 entries -- the in-band ones flagged, counted by
+// a scan and appended (key, entry, replicate, value) to the earlier ones.
+int union_stage_replicate(UnionCall& u, int r) {
+  h3d_ctx* ctx = u.ctx;
+  hipStream_t s = u.s;
+  PrepUnion& P = ctx->prep;
+  const int64_t m = u.nnz[r];
+  HIP_TRY(hipMemcpyAsync(u.d_indptr, u.indptr[r], (size_t)(u.n_bins + 1) * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(u.d_col, u.indices[r], m * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(u.d_val, u.data[r], m * 8, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_csr_rows, dim3((u.n_bins + 255) / 256), dim3(256), 0, s, u.d_indptr,
+                     u.n_bins, u.d_row);
+  hipLaunchKernelGGL(k_union_flags, dim3(grid_for(ctx, m)), dim3(kBlock), 0, s, u.d_row,
+                     u.d_col, u.d_val, m, u.n_bins, u.dist_max, u.d_flag);
+  if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(tmp, tb, u.d_flag, u.d_pos, (int)m, s);
+      }))
+    return rc;
+  int32_t last[2] = {0, 0};
+  if (int rc = d2h_sync(ctx, &last[0], u.d_pos + m - 1, 4, s)) return rc;
+  if (int rc = d2h_sync(ctx, &last[1], u.d_flag + m - 1, 4, s)) return rc;
+  const int64_t kept = (int64_t)last[0] + last[1], tot = u.tot;
+  if (tot + kept >= ((int64_t)1 << 31)) return fail(H3D_EARG, "too many in-band entries");
+  // the kept-entry arrays grow (keeping what earlier replicates wrote)
+  const size_t need = (size_t)std::max<int64_t>(tot + kept, 1);
+  Scratch sc{ctx};
+  u.d_keys = sc.keep<int64_t>("u_keys", need, tot);
+  u.d_ent = sc.keep<int32_t>("u_ent", need, tot);
+  P.ent_rep = sc.keep<int32_t>("u_ent_rep", need, tot);
+  P.ent_val = sc.keep<double>("u_ent_val", need, tot);
+  if (!sc.ok) return fail(H3D_ENOMEM, "union entries");
+  hipLaunchKernelGGL(k_union_keys, dim3(grid_for(ctx, m)), dim3(kBlock), 0, s, u.d_row, u.d_col,
+                     u.d_val, u.d_flag, u.d_pos, m, tot, r, u.n_bins, u.d_keys, u.d_ent,
+                     P.ent_rep, P.ent_val);
+  // the staging buffers are reused by the next replicate
+  HIP_TRY(hipStreamSynchronize(s));
+  u.tot += kept;
+  return 0;
+}
+
+// Stage (tot > 0 entries): the entries sorted by pixel key, the heads of the
+// runs of equal keys and the runs' count.
+int union_sort_runs(UnionCall& u) {
+  h3d_ctx* ctx = u.ctx;
+  hipStream_t s = u.s;
+  PrepUnion& P = ctx->prep;
+  const int64_t tot = u.tot;
+  Scratch sc{ctx};
+  P.keys_sorted = sc.get<int64_t>("u_keys_s", tot);
+  P.ent_sorted = sc.get<int32_t>("u_ent_s", tot);
+  u.d_head = sc.get<int32_t>("u_head", tot);
+  P.run_of = sc.get<int32_t>("u_run_incl", tot);
+  if (!sc.ok) return fail(H3D_ENOMEM, "union scratch");
+  if (int rc = cub_call(ctx, "cub_tmp_u", [&](void* tmp, size_t& tb) {
+        return hipcub::DeviceRadixSort::SortPairs(tmp, tb, u.d_keys, P.keys_sorted, u.d_ent,
+                                                  P.ent_sorted, (int)tot, 0, u.end_bit, s);
+      }))
+    return rc;
+  hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, tot)), dim3(kBlock), 0, s, P.keys_sorted,
+                     tot, u.sentinel, u.d_head);
+  if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& tb) {
+        return hipcub::DeviceScan::InclusiveSum(tmp, tb, u.d_head, P.run_of, (int)tot, s);
+      }))
+    return rc;
+  int32_t n_runs = 0;
+  if (int rc = d2h_sync(ctx, &n_runs, P.run_of + tot - 1, 4, s)) return rc;
+  P.n_runs = n_runs;
+  return 0;
+}
+
+// Stage (tot > 0): the runs that are pixels of the union -- flagged in
+// "u_keep", which h3d_union_fill takes by its slot -- and their count.
+int union_keep_runs(UnionCall& u) {
+  h3d_ctx* ctx = u.ctx;
+  hipStream_t s = u.s;
+  PrepUnion& P = ctx->prep;
+  const int64_t n_runs = P.n_runs, tot = u.tot;
+  Scratch sc{ctx};
+  P.run_start = sc.get<int64_t>("u_run_start", std::max<int64_t>(n_runs, 1));
+  int32_t* keep = sc.get<int32_t>("u_keep", std::max<int64_t>(n_runs, 1));
+  P.px_of_run = sc.get<int32_t>("u_px_incl", std::max<int64_t>(n_runs, 1));
+  if (!sc.ok) return fail(H3D_ENOMEM, "runs");
+  if (n_runs == 0) return 0;
+  hipLaunchKernelGGL(k_run_starts, dim3(grid_for(ctx, tot)), dim3(kBlock), 0, s, u.d_head,
+                     P.run_of, tot, P.run_start);
+  hipLaunchKernelGGL(k_run_keep, dim3(grid_for(ctx, n_runs)), dim3(kBlock), 0, s,
+                     P.keys_sorted, P.ent_sorted, P.run_start, n_runs, tot, u.sentinel,
+                     P.ent_rep, P.ent_val, u.R, u.n_bins, P.bias, keep);
+  if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& tb) {
+        return hipcub::DeviceScan::InclusiveSum(tmp, tb, keep, P.px_of_run, (int)n_runs, s);
+      }))
+    return rc;
+  int32_t n_px = 0;
+  if (int rc = d2h_sync(ctx, &n_px, P.px_of_run + n_runs - 1, 4, s)) return rc;
+  P.n_px = n_px;
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int h3d_union_count(h3d_ctx* ctx, int R, int n_bins,
                     const int64_t* const* indptr, const int32_t* const* indices,
                     const double* const* data, const int64_t* nnz,
                     const double* bias, int dist_max, int64_t* n_px_out) {
-  if (!ctx || !indptr || !indices || !data || !nnz || !bias || !n_px_out)
-    return fail(H3D_EARG, "null argument");
-  if (R < 1 || R > kMaxReps || n_bins < 1 || dist_max < 0)
-    return fail(H3D_EARG, "R=%d n_bins=%d dist_max=%d", R, n_bins, dist_max);
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  PrepUnion& P = ctx->prep;
-  P = PrepUnion();
-  P.R = R;
-  P.n_bins = n_bins;
-  int64_t max_m = 0;
-  for (int r = 0; r < R; ++r) {
-    if (nnz[r] < 0 || (nnz[r] > 0 && (!indices[r] || !data[r])) || !indptr[r])
-      return fail(H3D_EARG, "replicate %d CSR", r);
-    if (indptr[r][n_bins] != nnz[r]) return fail(H3D_EARG, "replicate %d indptr[-1] != nnz", r);
-    if (nnz[r] >= ((int64_t)1 << 31)) return fail(H3D_EARG, "replicate %d: too many entries", r);
-    max_m = std::max(max_m, nnz[r]);
+  if (!n_px_out) return fail(H3D_EARG, "null argument");
+  UnionCall u{ctx, R, n_bins, indptr, indices, data, nnz, bias, dist_max};
+  if (int rc = union_check_and_staging(u)) return rc;
+  for (int r = 0; r < R; ++r)
+    if (nnz[r] > 0)
+      if (int rc = union_stage_replicate(u, r)) return rc;
+  ctx->prep.n_entries = u.tot;
+  if (u.tot > 0) {
+    if (int rc = union_sort_runs(u)) return rc;
+    if (int rc = union_keep_runs(u)) return rc;
   }
-  const int64_t sentinel = (int64_t)n_bins * n_bins;
-  int end_bit = 1;
-  while (end_bit < 63 && (((int64_t)1) << end_bit) <= sentinel) ++end_bit;
-  // per-replicate staging (reused): only the in-band entries reach the
-  // per-entry key / sort / scan buffers, so their size and the 2^31 cap
-  // follow the band, not the whole-chromosome nnz
-  const size_t mm = (size_t)std::max<int64_t>(max_m, 1);
-  double* d_bias = (double*)scratch(ctx, "u_bias", (size_t)n_bins * R * 8);
-  int64_t* d_indptr = (int64_t*)scratch(ctx, "u_indptr", (size_t)(n_bins + 1) * 8);
-  int32_t* d_row = (int32_t*)scratch(ctx, "u_row_of", mm * 4);
-  int32_t* d_col = (int32_t*)scratch(ctx, "u_col", mm * 4);
-  double* d_val = (double*)scratch(ctx, "u_val_in", mm * 8);
-  int32_t* d_flag = (int32_t*)scratch(ctx, "u_flag", mm * 4);
-  int32_t* d_pos = (int32_t*)scratch(ctx, "u_pos", mm * 4);
-  int32_t* d_cnt = (int32_t*)scratch(ctx, "u_cnt", 4);
-  if (!d_bias || !d_indptr || !d_row || !d_col || !d_val || !d_flag || !d_pos || !d_cnt)
-    return fail(H3D_ENOMEM, "union staging");
-  P.bias = d_bias;
-  if (int rc = h2d_pinned(ctx, d_bias, bias, (size_t)n_bins * R * 8, s)) return rc;
-  int64_t tot = 0;  // kept entries so far
-  int64_t* d_keys = nullptr;
-  int32_t* d_ent = nullptr;
-  for (int r = 0; r < R; ++r) {
-    const int64_t m = nnz[r];
-    if (m == 0) continue;
-    HIP_TRY(hipMemcpyAsync(d_indptr, indptr[r], (size_t)(n_bins + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_col, indices[r], m * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_val, data[r], m * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_csr_rows, dim3((n_bins + 255) / 256), dim3(256), 0, s,
-                       d_indptr, n_bins, d_row);
-    hipLaunchKernelGGL(k_union_flags, dim3(grid_for(ctx, m)), dim3(kBlock), 0, s, d_row,
-                       d_col, d_val, m, n_bins, dist_max, d_flag);
-    size_t tbs = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tbs, d_flag, d_pos, (int)m, s));
-    void* tmps = scratch(ctx, "cub_tmp_s", tbs);
-    if (!tmps) return fail(H3D_ENOMEM, "scan temp");
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmps, tbs, d_flag, d_pos, (int)m, s));
-    int32_t last[2] = {0, 0};
-    if (int rc = d2h_sync(ctx, &last[0], d_pos + m - 1, 4, s)) return rc;
-    if (int rc = d2h_sync(ctx, &last[1], d_flag + m - 1, 4, s)) return rc;
-    const int64_t kept = (int64_t)last[0] + last[1];
-    if (tot + kept >= ((int64_t)1 << 31)) return fail(H3D_EARG, "too many in-band entries");
-    // the kept-entry arrays grow (keeping what earlier replicates wrote)
-    const size_t need = (size_t)std::max<int64_t>(tot + kept, 1);
-    d_keys = (int64_t*)scratch_keep(ctx, "u_keys", need * 8, tot * 8);
-    d_ent = (int32_t*)scratch_keep(ctx, "u_ent", need * 4, tot * 4);
-    P.ent_rep = (int32_t*)scratch_keep(ctx, "u_ent_rep", need * 4, tot * 4);
-    P.ent_val = (double*)scratch_keep(ctx, "u_ent_val", need * 8, tot * 8);
-    if (!d_keys || !d_ent || !P.ent_rep || !P.ent_val) return fail(H3D_ENOMEM, "union entries");
-    hipLaunchKernelGGL(k_union_keys, dim3(grid_for(ctx, m)), dim3(kBlock), 0, s, d_row, d_col,
-                       d_val, d_flag, d_pos, m, tot, r, n_bins, d_keys, d_ent, P.ent_rep,
-                       P.ent_val);
-    // the staging buffers are reused by the next replicate
-    HIP_TRY(hipStreamSynchronize(s));
-    tot += kept;
-  }
-  P.n_entries = tot;
-  if (tot == 0) {
-    P.n_px = 0;
-    *n_px_out = 0;
-    return 0;
-  }
-  P.keys_sorted = (int64_t*)scratch(ctx, "u_keys_s", tot * 8);
-  P.ent_sorted = (int32_t*)scratch(ctx, "u_ent_s", tot * 4);
-  int32_t* d_head = (int32_t*)scratch(ctx, "u_head", tot * 4);
-  P.run_of = (int32_t*)scratch(ctx, "u_run_incl", tot * 4);
-  if (!P.keys_sorted || !P.ent_sorted || !d_head || !P.run_of)
-    return fail(H3D_ENOMEM, "union scratch");
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_keys, P.keys_sorted, d_ent,
-                                             P.ent_sorted, (int)tot, 0, end_bit, s));
-  void* tmp = scratch(ctx, "cub_tmp_u", tb);
-  if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, d_keys, P.keys_sorted, d_ent,
-                                             P.ent_sorted, (int)tot, 0, end_bit, s));
-  hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, tot)), dim3(kBlock), 0, s,
-                     P.keys_sorted, tot, sentinel, d_head);
-  tb = 0;
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_head, P.run_of, (int)tot, s));
-  tmp = scratch(ctx, "cub_tmp_s", tb);
-  if (!tmp) return fail(H3D_ENOMEM, "scan temp");
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, tb, d_head, P.run_of, (int)tot, s));
-  int32_t n_runs = 0;
-  if (int rc = d2h_sync(ctx, &n_runs, P.run_of + tot - 1, 4, s)) return rc;
-  P.n_runs = n_runs;
-  P.run_start = (int64_t*)scratch(ctx, "u_run_start", std::max<int64_t>(n_runs, 1) * 8);
-  int32_t* keep = (int32_t*)scratch(ctx, "u_keep", std::max<int64_t>(n_runs, 1) * 4);
-  P.px_of_run = (int32_t*)scratch(ctx, "u_px_incl", std::max<int64_t>(n_runs, 1) * 4);
-  if (!P.run_start || !keep || !P.px_of_run) return fail(H3D_ENOMEM, "runs");
-  if (n_runs == 0) {
-    P.n_px = 0;
-    *n_px_out = 0;
-    return 0;
-  }
-  hipLaunchKernelGGL(k_run_starts, dim3(grid_for(ctx, tot)), dim3(kBlock), 0, s,
-                     d_head, P.run_of, tot, P.run_start);
-  hipLaunchKernelGGL(k_run_keep, dim3(grid_for(ctx, n_runs)), dim3(kBlock), 0, s,
-                     P.keys_sorted, P.ent_sorted, P.run_start, (int64_t)n_runs, tot,
-                     sentinel, P.ent_rep, P.ent_val, R, n_bins, d_bias, keep);
-  tb = 0;
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, keep, P.px_of_run, (int)n_runs, s));
-  tmp = scratch(ctx, "cub_tmp_s", tb);
-  if (!tmp) return fail(H3D_ENOMEM, "scan temp");
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, tb, keep, P.px_of_run, (int)n_runs, s));
-  int32_t n_px = 0;
-  if (int rc = d2h_sync(ctx, &n_px, P.px_of_run + n_runs - 1, 4, s)) return rc;
-  P.n_px = n_px;
-  *n_px_out = n_px;
+  *n_px_out = ctx->prep.n_px;
   return 0;
 }
 
@@ -174,13 +226,15 @@ int h3d_union_fill_dev(h3d_ctx* ctx, int32_t* row, int32_t* col, int64_t* raw,
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int R = P.R;
-  int32_t* d_row = (int32_t*)scratch(ctx, "u_out_row", n_px * 4);
-  int32_t* d_col = (int32_t*)scratch(ctx, "u_out_col", n_px * 4);
-  int64_t* d_raw = (int64_t*)scratch(ctx, "u_out_raw", n_px * R * 8);
-  double* d_bal = (double*)scratch(ctx, "u_out_bal", n_px * R * 8);
-  int32_t* keep = (int32_t*)scratch(ctx, "u_keep", std::max<int64_t>(P.n_runs, 1) * 4);
-  int* d_ovf = (int*)scratch(ctx, "ovf", 4);
-  if (!d_row || !d_col || !d_raw || !d_bal || !d_ovf) return fail(H3D_ENOMEM, "union out");
+  Scratch sc{ctx};
+  int32_t* d_row = sc.get<int32_t>("u_out_row", n_px);
+  int32_t* d_col = sc.get<int32_t>("u_out_col", n_px);
+  int64_t* d_raw = sc.get<int64_t>("u_out_raw", n_px * R);
+  double* d_bal = sc.get<double>("u_out_bal", n_px * R);
+  // (h3d_union_count's flags, by their slot)
+  int32_t* keep = sc.get<int32_t>("u_keep", std::max<int64_t>(P.n_runs, 1));
+  int* d_ovf = sc.get<int>("ovf", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "union out");
   hipLaunchKernelGGL(k_union_fill, dim3(grid_for(ctx, P.n_runs)), dim3(kBlock), 0, s,
                      P.keys_sorted, P.ent_sorted, P.run_start, keep, P.px_of_run,
                      P.n_runs, P.n_entries, P.ent_rep, P.ent_val, R, P.n_bins, P.bias,
@@ -193,10 +247,8 @@ int h3d_union_fill_dev(h3d_ctx* ctx, int32_t* row, int32_t* col, int64_t* raw,
     HIP_TRY(hipMemcpyAsync(d_bal_out, d_bal, n_px * R * 8, hipMemcpyDeviceToDevice, s));
   int ovf = 0;
   if (d_raw_out) {
-    HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, s));
-    hipLaunchKernelGGL(k_i64_to_i32, dim3(grid_for(ctx, n_px * R)), dim3(kBlock), 0, s, d_raw,
-                       d_raw_out, n_px * R, d_ovf);
-    HIP_TRY(hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, s));
+    if (int rc = counts_to_i32(ctx, d_raw, d_raw_out, n_px * R, d_ovf)) return rc;
+    if (int rc = counts_ovf_copy(ctx, d_ovf, &ovf)) return rc;
   }
   HIP_TRY(hipMemcpyAsync(row, d_row, n_px * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(col, d_col, n_px * 4, hipMemcpyDeviceToHost, s));
@@ -226,22 +278,19 @@ int h3d_disp_pixels_dev(h3d_ctx* ctx, const int32_t* d_row, const int32_t* d_col
     return fail(H3D_EARG, "null device output");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int32_t* d_sel = (int32_t*)scratch(ctx, "dp_sel", (size_t)std::max<int64_t>(n, 1) * 4);
-  int32_t* d_cnt = (int32_t*)scratch(ctx, "dp_cnt", 4);
-  double* d_bias = (double*)scratch(ctx, "dp_bias", (size_t)n_bins * R * 8);
-  if (!d_sel || !d_cnt || !d_bias) return fail(H3D_ENOMEM, "disp pixel scratch");
+  Scratch sc{ctx};
+  int32_t* d_sel = sc.get<int32_t>("dp_sel", (size_t)std::max<int64_t>(n, 1));
+  int32_t* d_cnt = sc.get<int32_t>("dp_cnt", 1);
+  double* d_bias = sc.get<double>("dp_bias", (size_t)n_bins * R);
+  if (!sc.ok) return fail(H3D_ENOMEM, "disp pixel scratch");
   if (int rc = h2d_pinned(ctx, d_bias, bias, (size_t)n_bins * R * 8, s)) return rc;
   hipcub::CountingInputIterator<int32_t> it(0);
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, d_disp_idx, d_sel, d_cnt, (int)n, s));
-  void* tmp = scratch(ctx, "cub_tmp_sel", tb);
-  if (!tmp) return fail(H3D_ENOMEM, "select temp");
-  HIP_TRY(hipcub::DeviceSelect::Flagged(tmp, tb, it, d_disp_idx, d_sel, d_cnt, (int)n, s));
-  int32_t* land = (int32_t*)pinned_rd(ctx, 4);
-  if (!land) return fail(H3D_ENOMEM, "pinned landing zone");
-  HIP_TRY(hipMemcpyAsync(land, d_cnt, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int32_t cnt = land[0];
+  if (int rc = cub_call(ctx, "cub_tmp_sel", [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceSelect::Flagged(tmp, bytes, it, d_disp_idx, d_sel, d_cnt, (int)n, s);
+      }))
+    return rc;
+  int32_t cnt = 0;
+  if (int rc = d2h_sync(ctx, &cnt, d_cnt, 4, s)) return rc;
   if (cnt != n_disp)
     return fail(H3D_EARG, "disp_idx selects %d pixels, caller expects %lld", cnt,
                 (long long)n_disp);
@@ -267,8 +316,9 @@ int h3d_pixel_f_dev(h3d_ctx* ctx, const int32_t* d_row, const int32_t* d_dist,
     return fail(H3D_EARG, "null device pointer");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int* d_bad = (int*)scratch(ctx, "pf_bad", 4);
-  if (!d_bad) return fail(H3D_ENOMEM, "pixel f scratch");
+  Scratch sc{ctx};
+  int* d_bad = sc.get<int>("pf_bad", 1);
+  if (!sc.ok) return fail(H3D_ENOMEM, "pixel f scratch");
   HIP_TRY(hipMemsetAsync(d_bad, 0, 4, s));
   hipLaunchKernelGGL(k_pixel_f, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_row, d_dist,
                      d_chrom, d_sfi, n, R, d_bias, d_boff, d_sf, d_soff, nchrom, d_f_out,
@@ -307,10 +357,10 @@ int h3d_scale_disp_dev(h3d_ctx* ctx, const double* d_balanced, const double* d_s
   a.dist_min = dist_thresh_min;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  double* d_scaled =
-      d_scaled_out ? d_scaled_out : (double*)scratch(ctx, "sd_scaled", (size_t)n * R * 8);
-  uint8_t* d_flag = d_flag_out ? d_flag_out : (uint8_t*)scratch(ctx, "sd_flag", (size_t)n);
-  if (!d_scaled || !d_flag) return fail(H3D_ENOMEM, "scale / disp scratch");
+  Scratch sc{ctx};
+  double* d_scaled = d_scaled_out ? d_scaled_out : sc.get<double>("sd_scaled", (size_t)n * R);
+  uint8_t* d_flag = d_flag_out ? d_flag_out : sc.get<uint8_t>("sd_flag", (size_t)n);
+  if (!sc.ok) return fail(H3D_ENOMEM, "scale / disp scratch");
   hipLaunchKernelGGL(k_scale_disp, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_balanced,
                      d_sf, sf_per_rep, d_row, d_col, n, R, a, d_scaled, d_flag);
   HIP_TRY(hipGetLastError());
@@ -337,11 +387,283 @@ int h3d_table_gather_dev(h3d_ctx* ctx, const double* d_tables, int D, int C,
   return 0;
 }
 
+}  // extern "C"
+
 namespace {
+
+// The size factors of every norm (util/scaling.py). size_factors_impl reads
+// as its stages; what they share travels in an SfCall.
+struct SfCall {
+  h3d_ctx* ctx;  // the request (balanced on the host or on the device)
+  const double *balanced, *d_balanced;
+  const int32_t* dist;
+  int64_t n;
+  int R, norm, n_bins;
+  double *sf_out, *d_sf_out;
+  hipStream_t s = nullptr;
+  // per-distance factors (n, R), else one set (R,); by median of ratios, else
+  // by simple scaling
+  bool conditional = false, mor = false;
+  const double* bal = nullptr;  // balanced on the device
+  // the pixels in (stable) distance order: sorted position k is pixel
+  // perm[k] at distance dist_s[k] in bin bin[k]; idx = 0 .. n - 1
+  int32_t *d_dist = nullptr, *d_dist_s = nullptr, *d_idx = nullptr, *d_perm = nullptr,
+          *d_bin = nullptr;
+  int nb = 1;
+  int64_t* d_bstart = nullptr;  // nb + 1 bin bounds (sorted positions)
+  std::vector<int64_t> bstart;
+  double *d_spb = nullptr, *d_dpb = nullptr;
+  std::vector<double> spb;  // per-bin factors (nb, R)
+  double* d_sf = nullptr;   // per-pixel factors (n, R)
+};
+
+// the (R,) factors of the global norms into the caller's device copy too
+int sf_global_out(SfCall& c) {
+  if (c.d_sf_out) {
+    HIP_TRY(hipSetDevice(c.ctx->device));
+    HIP_TRY(hipMemcpyAsync(c.d_sf_out, c.sf_out, c.R * 8, hipMemcpyHostToDevice,
+                           c.ctx->stream));
+    HIP_TRY(hipStreamSynchronize(c.ctx->stream));
+  }
+  return 0;
+}
+
+// Stage: the argument checks and the results that need no data pass
+// (*done: the call is complete).
+int sf_check_and_trivial(SfCall& c, bool* done) {
+  const int R = c.R, norm = c.norm;
+  c.conditional = norm == H3D_NORM_CONDITIONAL_MOR || norm == H3D_NORM_CONDITIONAL_SCALING;
+  c.mor = norm == H3D_NORM_CONDITIONAL_MOR || norm == H3D_NORM_MEDIAN_OF_RATIOS;
+  // sf_out may be NULL for the conditional norms when d_sf_out is given (the
+  // caller fetches the (n, R) factors in the background)
+  if (!c.ctx || (c.n > 0 && !c.balanced && !c.d_balanced) ||
+      (!c.sf_out && !(c.conditional && c.d_sf_out)))
+    return fail(H3D_EARG, "null argument");
+  if (R < 1 || R > kMaxReps || c.n_bins < 0)
+    return fail(H3D_EARG, "R=%d n_bins=%d", R, c.n_bins);
+  if (norm < H3D_NORM_CONDITIONAL_MOR || norm > H3D_NORM_NO_SCALING)
+    return fail(H3D_EARG, "norm %d", norm);
+  *done = true;
+  if (norm == H3D_NORM_NO_SCALING) {  // scaling.py:24: ones(R), no data pass
+    for (int r = 0; r < R; ++r) c.sf_out[r] = 1.0;
+    return sf_global_out(c);
+  }
+  if (c.conditional && c.n > 0 && !c.dist) return fail(H3D_EARG, "null dist");
+  if (c.n == 0) {
+    if (c.conditional) return 0;
+    for (int r = 0; r < R; ++r) c.sf_out[r] = NAN;  // median / sums of nothing
+    return sf_global_out(c);
+  }
+  if (c.n >= ((int64_t)1 << 31) / R) return fail(H3D_EARG, "n too large");
+  *done = false;
+  return 0;
+}
+
+// Stage: the distance order and the bins over it -- one bin holding every
+// pixel in the original order (the global norms), n_bins equal-count bins, or
+// one bin per distance -- and the bins' bounds, on the host too.
+int sf_order_and_bins(SfCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  const int64_t n = c.n;
+  const int R = c.R;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = c.s = ctx->stream;
+  Scratch sc{ctx};
+  double* d_bal = c.d_balanced ? nullptr : sc.get<double>("sf_bal", n * R);
+  c.d_dist = sc.get<int32_t>("sf_dist", n);
+  c.d_dist_s = sc.get<int32_t>("sf_dist_s", n);
+  c.d_idx = sc.get<int32_t>("sf_idx", n);
+  c.d_perm = sc.get<int32_t>("sf_perm", n);
+  c.d_bin = sc.get<int32_t>("sf_bin", n);
+  c.d_sf = sc.get<double>("sf_out", n * R);
+  if (!sc.ok) return fail(H3D_ENOMEM, "size factor scratch");
+  if (!c.d_balanced)
+    HIP_TRY(hipMemcpyAsync(d_bal, c.balanced, n * R * 8, hipMemcpyHostToDevice, s));
+  c.bal = c.d_balanced ? c.d_balanced : d_bal;
+  hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_idx, n);
+  if (!c.conditional) {
+    HIP_TRY(hipMemcpyAsync(c.d_perm, c.d_idx, n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemsetAsync(c.d_bin, 0, n * 4, s));
+  } else {
+    if (int rc = h2d_pinned(ctx, c.d_dist, c.dist, n * 4, s)) return rc;
+    // stable sort by distance (the pinned equal_bin tie order)
+    if (int rc = cub_call(ctx, "cub_tmp_sf", [&](void* tmp, size_t& bytes) {
+          return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, c.d_dist, c.d_dist_s, c.d_idx,
+                                                    c.d_perm, (int)n, 0, 31, s);
+        }))
+      return rc;
+    if (c.n_bins > 0) {
+      c.nb = c.n_bins;
+      hipLaunchKernelGGL(k_equal_bin, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, n, c.n_bins,
+                         c.d_bin);
+    } else {
+      int32_t* d_head = sc.get<int32_t>("sf_head", n);
+      if (!sc.ok) return fail(H3D_ENOMEM, "heads");
+      hipLaunchKernelGGL(k_dist_heads, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_dist_s,
+                         n, d_head);
+      if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& bytes) {
+            return hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_head, c.d_bin, (int)n, s);
+          }))
+        return rc;
+      hipLaunchKernelGGL(k_minus_one, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_bin, n);
+      int32_t last = 0;
+      if (int rc = d2h_sync(ctx, &last, c.d_bin + n - 1, 4, s)) return rc;
+      c.nb = last + 1;
+    }
+  }
+  const int nb = c.nb;
+  c.d_bstart = sc.get<int64_t>("sf_bstart", (size_t)(nb + 1));
+  c.d_spb = sc.get<double>("sf_spb", (size_t)nb * R);
+  c.d_dpb = sc.get<double>("sf_dpb", (size_t)nb);
+  if (!sc.ok) return fail(H3D_ENOMEM, "bins");
+  hipLaunchKernelGGL(k_bin_bounds, dim3((nb + 1 + 255) / 256), dim3(256), 0, s, c.d_bin, n, nb,
+                     c.d_bstart);
+  c.bstart.resize(nb + 1);
+  c.spb.resize((size_t)nb * R);
+  return d2h_sync(ctx, c.bstart.data(), c.d_bstart, (nb + 1) * 8, s);
+}
+
+// Stage: per-bin factors by median_of_ratios (scaling.py:27-47): per
+// replicate the median over the bin's all-positive rows of data / gmean(row);
+// a segmented sort of the ratios per (replicate, bin), invalid rows keyed
+// +inf past the valid ones
+int sf_bin_factors_mor(SfCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  hipStream_t s = c.s;
+  const int64_t n = c.n;
+  const int R = c.R, nb = c.nb;
+  Scratch sc{ctx};
+  int32_t* d_valid = sc.get<int32_t>("sf_valid", (size_t)nb);
+  double* d_keys = sc.get<double>("sf_keys", n * R);
+  double* d_keys_s = sc.get<double>("sf_keys_s", n * R);
+  int64_t* d_segb = sc.get<int64_t>("sf_segb", (size_t)nb * R);
+  int64_t* d_sege = sc.get<int64_t>("sf_sege", (size_t)nb * R);
+  if (!sc.ok) return fail(H3D_ENOMEM, "median scratch");
+  HIP_TRY(hipMemsetAsync(d_valid, 0, (size_t)nb * 4, s));
+  hipLaunchKernelGGL(k_mor_keys, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.bal, c.d_perm, n,
+                     R, c.d_bin, d_keys, d_valid);
+  std::vector<int64_t> segb((size_t)nb * R), sege((size_t)nb * R);
+  for (int r = 0; r < R; ++r)
+    for (int b = 0; b < nb; ++b) {
+      segb[(size_t)r * nb + b] = (int64_t)r * n + c.bstart[b];
+      sege[(size_t)r * nb + b] = (int64_t)r * n + c.bstart[b + 1];
+    }
+  if (int rc = h2d_pinned(ctx, d_segb, segb.data(), segb.size() * 8, s)) return rc;
+  if (int rc = h2d_pinned(ctx, d_sege, sege.data(), sege.size() * 8, s)) return rc;
+  if (int rc = cub_call(ctx, "cub_tmp_seg", [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, bytes, d_keys, d_keys_s,
+                                                          (int)(n * R), nb * R, d_segb, d_sege,
+                                                          0, 64, s);
+      }))
+    return rc;
+  hipLaunchKernelGGL(k_mor_median, dim3((nb * R + 255) / 256), dim3(256), 0, s, d_keys_s,
+                     c.d_bstart, d_valid, nb, n, R, c.d_spb);
+  return d2h_sync(ctx, c.spb.data(), c.d_spb, (size_t)nb * R * 8, s);
+}
+
+// Stage: per-bin factors by simple_scaling (scaling.py:50-65): column sums
+// over the bin's rows in their original order (members grouped by bin: a
+// stable sort of the original-order bin labels), then s / gmean(s,
+// pseudocount 1)
+int sf_bin_factors_scaling(SfCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  hipStream_t s = c.s;
+  const int64_t n = c.n;
+  const int R = c.R, nb = c.nb;
+  int32_t* members = c.d_idx;
+  if (c.conditional) {
+    Scratch sc{ctx};
+    int32_t* d_bin_orig = sc.get<int32_t>("sf_bin_orig", n);
+    int32_t* d_bin_orig_s = sc.get<int32_t>("sf_bin_orig_s", n);
+    int32_t* d_iota = sc.get<int32_t>("sf_iota2", n);
+    members = sc.get<int32_t>("sf_members", n);
+    if (!sc.ok) return fail(H3D_ENOMEM, "member scratch");
+    hipLaunchKernelGGL(k_scatter_bin, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_perm,
+                       c.d_bin, n, d_bin_orig);
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_iota, n);
+    int end_bit = 1;
+    while (end_bit < 31 && (1 << end_bit) <= nb) ++end_bit;
+    if (int rc = cub_call(ctx, "cub_tmp_sf", [&](void* tmp, size_t& bytes) {
+          return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, d_bin_orig, d_bin_orig_s, d_iota,
+                                                    members, (int)n, 0, end_bit, s);
+        }))
+      return rc;
+  }
+  hipLaunchKernelGGL(k_bin_colsum, dim3((nb * R + 255) / 256), dim3(256), 0, s, c.bal, members,
+                     c.d_bstart, nb, R, c.d_spb);
+  std::vector<double> colsum((size_t)nb * R);
+  if (int rc = d2h_sync(ctx, colsum.data(), c.d_spb, (size_t)nb * R * 8, s)) return rc;
+  for (int b = 0; b < nb; ++b) {
+    const double* cs = &colsum[(size_t)b * R];
+    double lg[kMaxReps];
+    for (int r = 0; r < R; ++r) lg[r] = std::log(cs[r] + 1);
+    const double gm = std::exp(np_sum<kMaxReps>(lg, R) / R) - 1;
+    for (int r = 0; r < R; ++r) c.spb[(size_t)b * R + r] = cs[r] / gm;
+  }
+  return 0;
+}
+
+// Stage (the conditional norms): per-pixel factors (scaling.py:88-105) --
+// interpolated between the bins' mean distances, or each pixel its
+// distance's own -- and the copies to the caller.
+int sf_pixel_factors(SfCall& c) {
+  h3d_ctx* ctx = c.ctx;
+  hipStream_t s = c.s;
+  const int64_t n = c.n;
+  const int R = c.R, nb = c.nb;
+  if (c.n_bins > 0) {
+    hipLaunchKernelGGL(k_bin_dist_sum, dim3(nb), dim3(256), 0, s, c.d_dist_s, c.d_bstart, nb,
+                       c.d_dpb);
+    std::vector<double> dpb(nb);
+    HIP_TRY(hipMemcpyAsync(dpb.data(), c.d_dpb, nb * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // np.unique(bins): only non-empty bins take part in the interpolation
+    std::vector<double> xp, yp;
+    for (int b = 0; b < nb; ++b)
+      if (c.bstart[b + 1] > c.bstart[b]) {
+        xp.push_back(dpb[b]);
+        for (int r = 0; r < R; ++r) yp.push_back(c.spb[(size_t)b * R + r]);
+      }
+    const int m = (int)xp.size();
+    if (m < 2) return fail(H3D_EARG, "fewer than two distance bins to interpolate");
+    Scratch sc{ctx};
+    double* d_xp = sc.get<double>("sf_xp", m);
+    double* d_yp = sc.get<double>("sf_yp", (size_t)m * R);
+    if (!sc.ok) return fail(H3D_ENOMEM, "interp");
+    HIP_TRY(hipMemcpyAsync(d_xp, xp.data(), m * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_yp, yp.data(), (size_t)m * R * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_sf_interp, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_dist, n, R,
+                       d_xp, d_yp, m, c.d_sf);
+  } else {
+    HIP_TRY(hipMemcpyAsync(c.d_spb, c.spb.data(), (size_t)nb * R * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_sf_exact, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_perm, c.d_bin,
+                       n, R, c.d_spb, c.d_sf);
+  }
+  if (c.d_sf_out)
+    HIP_TRY(hipMemcpyAsync(c.d_sf_out, c.d_sf, n * R * 8, hipMemcpyDeviceToDevice, s));
+  if (c.sf_out) HIP_TRY(hipMemcpyAsync(c.sf_out, c.d_sf, n * R * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
 int size_factors_impl(h3d_ctx* ctx, const double* balanced, const double* d_balanced,
                       const int32_t* dist, int64_t n, int R, int norm, int n_bins,
-                      double* sf_out, double* d_sf_out);
+                      double* sf_out, double* d_sf_out) {
+  SfCall c{ctx, balanced, d_balanced, dist, n, R, norm, n_bins, sf_out, d_sf_out};
+  bool done = false;
+  if (int rc = sf_check_and_trivial(c, &done)) return rc;
+  if (done) return 0;
+  if (int rc = sf_order_and_bins(c)) return rc;
+  if (int rc = c.mor ? sf_bin_factors_mor(c) : sf_bin_factors_scaling(c)) return rc;
+  if (c.conditional) return sf_pixel_factors(c);
+  // a global norm: the one bin's factors are the result
+  std::memcpy(sf_out, c.spb.data(), R * 8);
+  return sf_global_out(c);
+}
+
 }  // namespace
+
+extern "C" {
 
 int h3d_size_factors(h3d_ctx* ctx, const double* balanced, const int32_t* dist,
                      int64_t n, int R, int norm, int n_bins, double* sf_out) {
@@ -356,220 +678,6 @@ int h3d_size_factors_dev(h3d_ctx* ctx, const double* d_balanced, const int32_t* 
   return size_factors_impl(ctx, nullptr, d_balanced, dist, n, R, norm, n_bins, sf_out,
                            d_sf_out);
 }
-
-}  // extern "C"
-
-namespace {
-int size_factors_impl(h3d_ctx* ctx, const double* balanced, const double* d_balanced,
-                      const int32_t* dist, int64_t n, int R, int norm, int n_bins,
-                      double* sf_out, double* d_sf_out) {
-  const bool cond_norm =
-      norm == H3D_NORM_CONDITIONAL_MOR || norm == H3D_NORM_CONDITIONAL_SCALING;
-  // sf_out may be NULL for the conditional norms when d_sf_out is given (the
-  // caller fetches the (n, R) factors in the background)
-  if (!ctx || (n > 0 && !balanced && !d_balanced) || (!sf_out && !(cond_norm && d_sf_out)))
-    return fail(H3D_EARG, "null argument");
-  if (R < 1 || R > kMaxReps || n_bins < 0) return fail(H3D_EARG, "R=%d n_bins=%d", R, n_bins);
-  if (norm < H3D_NORM_CONDITIONAL_MOR || norm > H3D_NORM_NO_SCALING)
-    return fail(H3D_EARG, "norm %d", norm);
-  const bool conditional =
-      norm == H3D_NORM_CONDITIONAL_MOR || norm == H3D_NORM_CONDITIONAL_SCALING;
-  const bool mor = norm == H3D_NORM_CONDITIONAL_MOR || norm == H3D_NORM_MEDIAN_OF_RATIOS;
-  // the (R,) factors of the global norms into the caller's device copy too
-  auto global_out = [&]() -> int {
-    if (d_sf_out) {
-      HIP_TRY(hipSetDevice(ctx->device));
-      HIP_TRY(hipMemcpyAsync(d_sf_out, sf_out, R * 8, hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return 0;
-  };
-  if (norm == H3D_NORM_NO_SCALING) {  // scaling.py:24: ones(R), no data pass
-    for (int r = 0; r < R; ++r) sf_out[r] = 1.0;
-    return global_out();
-  }
-  if (conditional && n > 0 && !dist) return fail(H3D_EARG, "null dist");
-  if (n == 0) {
-    if (!conditional) {
-      for (int r = 0; r < R; ++r) sf_out[r] = NAN;  // median / sums of nothing
-      return global_out();
-    }
-    return 0;
-  }
-  if (n >= ((int64_t)1 << 31) / R) return fail(H3D_EARG, "n too large");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  double* d_bal = d_balanced ? nullptr : (double*)scratch(ctx, "sf_bal", n * R * 8);
-  int32_t* d_dist = (int32_t*)scratch(ctx, "sf_dist", n * 4);
-  int32_t* d_dist_s = (int32_t*)scratch(ctx, "sf_dist_s", n * 4);
-  int32_t* d_idx = (int32_t*)scratch(ctx, "sf_idx", n * 4);
-  int32_t* d_perm = (int32_t*)scratch(ctx, "sf_perm", n * 4);
-  int32_t* d_bin = (int32_t*)scratch(ctx, "sf_bin", n * 4);
-  double* d_sf = (double*)scratch(ctx, "sf_out", n * R * 8);
-  if ((!d_balanced && !d_bal) || !d_dist || !d_dist_s || !d_idx || !d_perm || !d_bin || !d_sf)
-    return fail(H3D_ENOMEM, "size factor scratch");
-  if (!d_balanced)
-    HIP_TRY(hipMemcpyAsync(d_bal, balanced, n * R * 8, hipMemcpyHostToDevice, s));
-  const double* bal = d_balanced ? d_balanced : d_bal;
-  hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_idx, n);
-  size_t tb = 0;
-  void* tmp = nullptr;
-  // 1. bins over the (stable) distance order: sorted position k -> bin[k]
-  int nb = 1;
-  if (!conditional) {
-    // one bin holding every pixel, in the original order
-    HIP_TRY(hipMemcpyAsync(d_perm, d_idx, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_bin, 0, n * 4, s));
-  } else {
-    if (int rc = h2d_pinned(ctx, d_dist, dist, n * 4, s)) return rc;
-    // stable sort by distance (the pinned equal_bin tie order)
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_dist, d_dist_s, d_idx,
-                                               d_perm, (int)n, 0, 31, s));
-    tmp = scratch(ctx, "cub_tmp_sf", tb);
-    if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, d_dist, d_dist_s, d_idx, d_perm,
-                                               (int)n, 0, 31, s));
-    if (n_bins > 0) {
-      nb = n_bins;
-      hipLaunchKernelGGL(k_equal_bin, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, n,
-                         n_bins, d_bin);
-    } else {
-      int32_t* d_head = (int32_t*)scratch(ctx, "sf_head", n * 4);
-      if (!d_head) return fail(H3D_ENOMEM, "heads");
-      hipLaunchKernelGGL(k_dist_heads, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         d_dist_s, n, d_head);
-      tb = 0;
-      HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_head, d_bin, (int)n, s));
-      tmp = scratch(ctx, "cub_tmp_s", tb);
-      if (!tmp) return fail(H3D_ENOMEM, "scan temp");
-      HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, tb, d_head, d_bin, (int)n, s));
-      hipLaunchKernelGGL(k_minus_one, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_bin, n);
-      int32_t last = 0;
-      if (int rc = d2h_sync(ctx, &last, d_bin + n - 1, 4, s)) return rc;
-      nb = last + 1;
-    }
-  }
-  int64_t* d_bstart = (int64_t*)scratch(ctx, "sf_bstart", (size_t)(nb + 1) * 8);
-  double* d_spb = (double*)scratch(ctx, "sf_spb", (size_t)nb * R * 8);
-  double* d_dpb = (double*)scratch(ctx, "sf_dpb", (size_t)nb * 8);
-  if (!d_bstart || !d_spb || !d_dpb) return fail(H3D_ENOMEM, "bins");
-  hipLaunchKernelGGL(k_bin_bounds, dim3((nb + 1 + 255) / 256), dim3(256), 0, s, d_bin,
-                     n, nb, d_bstart);
-  std::vector<int64_t> bstart(nb + 1);
-  if (int rc = d2h_sync(ctx, bstart.data(), d_bstart, (nb + 1) * 8, s)) return rc;
-  // 2. per-bin factors s_per_bin (nb, R)
-  std::vector<double> spb((size_t)nb * R);
-  if (mor) {
-    // median_of_ratios (scaling.py:27-47): per replicate the median over the
-    // bin's all-positive rows of data / gmean(row); a segmented sort of the
-    // ratios per (replicate, bin), invalid rows keyed +inf past the valid ones
-    int32_t* d_valid = (int32_t*)scratch(ctx, "sf_valid", (size_t)nb * 4);
-    double* d_keys = (double*)scratch(ctx, "sf_keys", n * R * 8);
-    double* d_keys_s = (double*)scratch(ctx, "sf_keys_s", n * R * 8);
-    int64_t* d_segb = (int64_t*)scratch(ctx, "sf_segb", (size_t)nb * R * 8);
-    int64_t* d_sege = (int64_t*)scratch(ctx, "sf_sege", (size_t)nb * R * 8);
-    if (!d_valid || !d_keys || !d_keys_s || !d_segb || !d_sege)
-      return fail(H3D_ENOMEM, "median scratch");
-    HIP_TRY(hipMemsetAsync(d_valid, 0, (size_t)nb * 4, s));
-    hipLaunchKernelGGL(k_mor_keys, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, bal,
-                       d_perm, n, R, d_bin, d_keys, d_valid);
-    std::vector<int64_t> segb((size_t)nb * R), sege((size_t)nb * R);
-    for (int r = 0; r < R; ++r)
-      for (int b = 0; b < nb; ++b) {
-        segb[(size_t)r * nb + b] = (int64_t)r * n + bstart[b];
-        sege[(size_t)r * nb + b] = (int64_t)r * n + bstart[b + 1];
-      }
-    if (int rc = h2d_pinned(ctx, d_segb, segb.data(), segb.size() * 8, s)) return rc;
-    if (int rc = h2d_pinned(ctx, d_sege, sege.data(), sege.size() * 8, s)) return rc;
-    tb = 0;
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb, d_keys, d_keys_s,
-                                                       (int)(n * R), nb * R, d_segb,
-                                                       d_sege, 0, 64, s));
-    tmp = scratch(ctx, "cub_tmp_seg", tb);
-    if (!tmp) return fail(H3D_ENOMEM, "segmented sort temp");
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, tb, d_keys, d_keys_s,
-                                                       (int)(n * R), nb * R, d_segb,
-                                                       d_sege, 0, 64, s));
-    hipLaunchKernelGGL(k_mor_median, dim3((nb * R + 255) / 256), dim3(256), 0, s,
-                       d_keys_s, d_bstart, d_valid, nb, n, R, d_spb);
-    if (int rc = d2h_sync(ctx, spb.data(), d_spb, (size_t)nb * R * 8, s)) return rc;
-  } else {
-    // simple_scaling (scaling.py:50-65): column sums over the bin's rows in
-    // their original order (members grouped by bin: a stable sort of the
-    // original-order bin labels), then s / gmean(s, pseudocount 1)
-    int32_t* members = d_idx;
-    if (conditional) {
-      int32_t* d_bin_orig = (int32_t*)scratch(ctx, "sf_bin_orig", n * 4);
-      int32_t* d_bin_orig_s = (int32_t*)scratch(ctx, "sf_bin_orig_s", n * 4);
-      int32_t* d_iota = (int32_t*)scratch(ctx, "sf_iota2", n * 4);
-      members = (int32_t*)scratch(ctx, "sf_members", n * 4);
-      if (!d_bin_orig || !d_bin_orig_s || !d_iota || !members)
-        return fail(H3D_ENOMEM, "member scratch");
-      hipLaunchKernelGGL(k_scatter_bin, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         d_perm, d_bin, n, d_bin_orig);
-      hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_iota, n);
-      int end_bit = 1;
-      while (end_bit < 31 && (1 << end_bit) <= nb) ++end_bit;
-      tb = 0;
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_bin_orig, d_bin_orig_s,
-                                                 d_iota, members, (int)n, 0, end_bit, s));
-      tmp = scratch(ctx, "cub_tmp_sf", tb);
-      if (!tmp) return fail(H3D_ENOMEM, "sort temp");
-      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, d_bin_orig, d_bin_orig_s, d_iota,
-                                                 members, (int)n, 0, end_bit, s));
-    }
-    hipLaunchKernelGGL(k_bin_colsum, dim3((nb * R + 255) / 256), dim3(256), 0, s, bal,
-                       members, d_bstart, nb, R, d_spb);
-    std::vector<double> colsum((size_t)nb * R);
-    if (int rc = d2h_sync(ctx, colsum.data(), d_spb, (size_t)nb * R * 8, s)) return rc;
-    for (int b = 0; b < nb; ++b) {
-      const double* cs = &colsum[(size_t)b * R];
-      double lg[kMaxReps];
-      for (int r = 0; r < R; ++r) lg[r] = std::log(cs[r] + 1);
-      const double gm = std::exp(np_sum<kMaxReps>(lg, R) / R) - 1;
-      for (int r = 0; r < R; ++r) spb[(size_t)b * R + r] = cs[r] / gm;
-    }
-  }
-  if (!conditional) {
-    std::memcpy(sf_out, spb.data(), R * 8);
-    return global_out();
-  }
-  // 3. per-pixel factors (scaling.py:88-105)
-  if (n_bins > 0) {
-    hipLaunchKernelGGL(k_bin_dist_sum, dim3(nb), dim3(256), 0, s, d_dist_s, d_bstart, nb,
-                       d_dpb);
-    std::vector<double> dpb(nb);
-    HIP_TRY(hipMemcpyAsync(dpb.data(), d_dpb, nb * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    // np.unique(bins): only non-empty bins take part in the interpolation
-    std::vector<double> xp, yp;
-    for (int b = 0; b < nb; ++b)
-      if (bstart[b + 1] > bstart[b]) {
-        xp.push_back(dpb[b]);
-        for (int r = 0; r < R; ++r) yp.push_back(spb[(size_t)b * R + r]);
-      }
-    const int m = (int)xp.size();
-    if (m < 2) return fail(H3D_EARG, "fewer than two distance bins to interpolate");
-    double* d_xp = (double*)scratch(ctx, "sf_xp", m * 8);
-    double* d_yp = (double*)scratch(ctx, "sf_yp", (size_t)m * R * 8);
-    if (!d_xp || !d_yp) return fail(H3D_ENOMEM, "interp");
-    HIP_TRY(hipMemcpyAsync(d_xp, xp.data(), m * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_yp, yp.data(), (size_t)m * R * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_sf_interp, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_dist, n,
-                       R, d_xp, d_yp, m, d_sf);
-  } else {
-    HIP_TRY(hipMemcpyAsync(d_spb, spb.data(), (size_t)nb * R * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_sf_exact, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_perm,
-                       d_bin, n, R, d_spb, d_sf);
-  }
-  if (d_sf_out) HIP_TRY(hipMemcpyAsync(d_sf_out, d_sf, n * R * 8, hipMemcpyDeviceToDevice, s));
-  if (sf_out) HIP_TRY(hipMemcpyAsync(sf_out, d_sf, n * R * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
-}
-}  // namespace
-
-extern "C" {
 
 int h3d_size_factors_cmor(h3d_ctx* ctx, const double* balanced,
                           const int32_t* dist, int64_t n, int R, int n_bins,

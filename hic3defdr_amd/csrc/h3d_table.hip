@@ -719,8 +719,9 @@ int h3d_disp_tables_dev(h3d_ctx* ctx, const double* d_disp_per_dist, int D, int 
     return fail(H3D_EARG, "null argument / D / C");
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int* d_status = (int*)scratch(ctx, "table_status", (size_t)kMaxConds * 4);
-  if (!d_status) return fail(H3D_ENOMEM, "table status");
+  Scratch sc{ctx};
+  int* d_status = sc.get<int>("table_status", kMaxConds);
+  if (!sc.ok) return fail(H3D_ENOMEM, "table status");
   ctx->tab_pending = {d_disp_per_dist, d_tables_out, D, C, weighted, frac,
                       auto_frac_factor, 1};
   if (D > kMaxD) {  // beyond the LDS working set: the host smoother
@@ -749,7 +750,7 @@ int h3d_disp_tables_dev(h3d_ctx* ctx, const double* d_disp_per_dist, int D, int 
     ProfScope ps(ctx, "disp_table", D);
     unsigned long long* d_stamps = nullptr;
     if (getenv("H3D_TABLE_STAMPS")) {
-      d_stamps = (unsigned long long*)scratch(ctx, "table_stamps", kMaxConds * kStamps * 8);
+      d_stamps = sc.get<unsigned long long>("table_stamps", kMaxConds * kStamps);
       if (d_stamps) HIP_TRY(hipMemsetAsync(d_stamps, 0, kMaxConds * kStamps * 8, s));
     }
     hipLaunchKernelGGL(k_disp_table, dim3(C), dim3(kThreads), lds_bytes(D), s,
@@ -769,7 +770,7 @@ namespace h3dint {
 int table_status_copy(h3d_ctx* ctx, int* h_st) {
   const TablePending& tp = ctx->tab_pending;
   if (!tp.active || tp.on_host) return 0;
-  const int* d_status = (const int*)scratch(ctx, "table_status", (size_t)kMaxConds * 4);
+  const int* d_status = Scratch{ctx}.get<int>("table_status", kMaxConds);
   HIP_TRY(hipMemcpyAsync(h_st, d_status, tp.C * 4, hipMemcpyDeviceToHost, ctx->stream));
   return 1;
 }
@@ -815,7 +816,8 @@ extern "C" int h3d_disp_tables_wait(h3d_ctx* ctx) {
   if (getenv("H3D_TABLE_STAMPS")) {  // per condition: us since the start
     using h3dtab::kStamps;
     unsigned long long h[kMaxConds * kStamps];
-    const void* d = h3dint::scratch(ctx, "table_stamps", kMaxConds * kStamps * 8);
+    const void* d = h3dint::Scratch{ctx}.get<unsigned long long>("table_stamps",
+                                                                 kMaxConds * kStamps);
     HIP_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
     for (int c = 0; c < ctx->tab_pending.C; ++c) {
       fprintf(stderr, "[h3d table] cond %d:", c);
