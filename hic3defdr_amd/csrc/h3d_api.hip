@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <optional>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -513,6 +514,30 @@ struct DispCall {
   SegState* h_sst = nullptr;
   int* h_bad = nullptr;
   bool have_res = false;  // the results of the final poll are in h_res
+  // the prep's profile scope: it ends with sort_and_gather, or -- a forked
+  // prep -- behind the join
+  std::optional<ProfScope> prep_scope;
+  // the prep's side branch (conditions 1 .. C-1 on ctx->prep_side) has not
+  // joined s yet
+  bool forked = false;
+  // The side branch back into s (nothing to do unless forked): s waits for
+  // all that the side stream holds, then disp_prep ends. The destructor
+  // joins on every path out of the call that did not get there, so no
+  // side-stream kernel outlives the call's claim on the scratch; where the
+  // wait cannot be enqueued, the host waits for the side stream instead.
+  void join_prep() {
+    if (forked) {
+      forked = false;
+      if (hipEventRecord(ctx->prep_join, ctx->prep_side) != hipSuccess ||
+          hipStreamWaitEvent(s, ctx->prep_join, 0) != hipSuccess)
+        (void)hipStreamSynchronize(ctx->prep_side);
+    }
+    prep_scope.reset();
+  }
+  DispCall() = default;
+  DispCall(const DispCall&) = delete;
+  DispCall& operator=(const DispCall&) = delete;
+  ~DispCall() { join_prep(); }
 };
 
 // the equalize pass (heavy: q2qnbinom) over the active work list, then
@@ -540,13 +565,45 @@ void launch_disp_work(const DispCall& c) {
 }
 
 // stable radix sort of (key, value) pairs over key bits [begin_bit, end_bit)
+// on stream s, its hipcub temp out of the slot tmp_slot
 template <typename K>
-int radix_sort_pairs(h3d_ctx* ctx, const K* keys_in, K* keys_out, const int32_t* vals_in,
-                     int32_t* vals_out, int64_t n, int begin_bit, int end_bit) {
-  return cub_call(ctx, "cub_tmp", [&](void* tmp, size_t& bytes) {
+int radix_sort_pairs(h3d_ctx* ctx, const char* tmp_slot, hipStream_t s, const K* keys_in,
+                     K* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n,
+                     int begin_bit, int end_bit) {
+  return cub_call(ctx, tmp_slot, [&](void* tmp, size_t& bytes) {
     return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out,
-                                              (int)n, begin_bit, end_bit, ctx->stream);
+                                              (int)n, begin_bit, end_bit, s);
   });
+}
+
+// the temp bytes radix_sort_pairs<K> takes for n pairs (reserved ahead of
+// the prep's fork: cub_call then finds its slot large enough)
+template <typename K>
+int radix_sort_temp_bytes(int64_t n, int begin_bit, int end_bit, size_t* bytes) {
+  return cub_bytes(
+      [&](void* tmp, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(tmp, b, (const K*)nullptr, (K*)nullptr,
+                                                  (const int32_t*)nullptr, (int32_t*)nullptr,
+                                                  (int)n, begin_bit, end_bit, (hipStream_t) nullptr);
+      },
+      bytes);
+}
+
+// The side stream and the two events of a forked prep, created on first use
+// (false: they cannot be had, the prep stays on one stream).
+bool prep_side_ready(h3d_ctx* ctx) {
+  if (!ctx->prep_side &&
+      hipStreamCreateWithFlags(&ctx->prep_side, hipStreamNonBlocking) != hipSuccess)
+    ctx->prep_side = nullptr;
+  if (!ctx->prep_fork &&
+      hipEventCreateWithFlags(&ctx->prep_fork, hipEventDisableTiming) != hipSuccess)
+    ctx->prep_fork = nullptr;
+  if (!ctx->prep_join &&
+      hipEventCreateWithFlags(&ctx->prep_join, hipEventDisableTiming) != hipSuccess)
+    ctx->prep_join = nullptr;
+  const bool ok = ctx->prep_side && ctx->prep_fork && ctx->prep_join;
+  if (!ok) (void)hipGetLastError();  // (not this call's error: it runs on one stream)
+  return ok;
 }
 
 int validate_and_plan(DispCall& c, const int32_t* cond_of_rep, int estimator) {
@@ -620,21 +677,65 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
   K* keys = sc.template get<K>("dkeys", (pack ? (size_t)C : 1) * n);
   K* keys_s = sc.template get<K>("dkeys_s", n);
   if (!sc.ok) return fail(H3D_ENOMEM, "sort keys");
-  for (int cc = 0; cc < C; ++cc) {
-    const int32_t* reps_c = d_reps + cc * kMaxReps;
-    K* keys_c = pack ? keys + (size_t)cc * n : keys;
+  // A branch of the prep: its stream and what its conditions, one after the
+  // other, write. idx_in, the packed records and their per-condition keys
+  // are only read after the key pass and are shared; the unpacked path's one
+  // key buffer is rewritten per condition, so the side branch has its own.
+  struct Branch {
+    hipStream_t s;
+    K *keys, *keys_s;
+    int32_t* idx_out;
+    const char* tmp_slot;
+  };
+  const Branch main{s, keys, keys_s, idx_out, "cub_tmp"};
+  Branch side = main;
+  // H3D_PREP_STREAMS=2: conditions 1 .. C-1 on the side stream. Every buffer
+  // of both branches, the hipcub temps included, is taken here, before the
+  // fork: no slot is regrown while a stream works on it. Without the extra
+  // buffers (or the stream) the prep stays on one stream, and so does a call
+  // of more than kPrepForkMaxPx pixels: the overlap wins a fixed amount per
+  // call (the sorts' short fill and histogram kernels, k_key_dist, launch
+  // gaps) and loses in proportion to n, since sort passes and gathers that
+  // each fill the chip slow each other down. Parent
+  // against two streams, prep per step: cfg2 (3.8 M pixels) 0.60 -> 0.51 ms,
+  // cfg4 (13 M, C = 3) 5.61 -> 5.44, cfg3 (46 M) 5.73 -> 6.04 (r10b).
+  constexpr int64_t kPrepForkMaxPx = (int64_t)1 << 24;
+  bool two = ctx->prep_streams == 2 && C > 1 && n <= kPrepForkMaxPx;
+  if (two) {
+    Scratch sb{ctx};
+    size_t tmp_bytes = 0;
+    side.keys_s = sb.template get<K>("dkeys_s_b", n);
+    side.idx_out = sb.template get<int32_t>("idx_out_b", n);
+    if (!pack) side.keys = sb.template get<K>("dkeys_b", n);
+    side.tmp_slot = "cub_tmp_b";
+    two = sb.ok && radix_sort_temp_bytes<K>(n, 0, sort_bits, &tmp_bytes) == 0 &&
+          scratch(ctx, main.tmp_slot, tmp_bytes) && scratch(ctx, side.tmp_slot, tmp_bytes) &&
+          prep_side_ready(ctx);
+    if (two) {
+      side.s = ctx->prep_side;
+    } else {
+      (void)hipGetLastError();  // (a failed allocation is not this call's error)
+      side = main;
+    }
+  }
+  auto key_pass = [&](int cc, const Branch& b) {
     if (!pack)
-      hipLaunchKernelGGL(k_dist_cond_keys<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         c.d_dist, c.d_raw, n, R, reps_c, c.nrep[cc], cbits, keys_c);
+      hipLaunchKernelGGL(k_dist_cond_keys<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s,
+                         c.d_dist, c.d_raw, n, R, d_reps + cc * kMaxReps, c.nrep[cc], cbits,
+                         b.keys);
     else if (cc == 0)  // (pack implies K = uint32_t)
-      hipLaunchKernelGGL(k_dist_cond_keys_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
+      hipLaunchKernelGGL(k_dist_cond_keys_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s,
                          c.d_dist, c.d_raw, c.d_f, n, R, C, d_reps, d_nrep,
                          reinterpret_cast<uint32_t*>(keys), packed);
-    if (int rc = radix_sort_pairs<K>(ctx, keys_c, keys_s, idx_in, idx_out, n, 0, sort_bits))
+  };
+  auto sort_gather = [&](int cc, const Branch& b) -> int {
+    const K* keys_c = pack ? keys + (size_t)cc * n : b.keys;
+    if (int rc = radix_sort_pairs<K>(ctx, b.tmp_slot, b.s, keys_c, b.keys_s, idx_in, b.idx_out,
+                                     n, 0, sort_bits))
       return rc;
     if (cc == 0)
-      hipLaunchKernelGGL(k_key_dist<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s,
-                         (const K*)keys_s, n, cbits, c.dist_s);
+      hipLaunchKernelGGL(k_key_dist<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s,
+                         (const K*)b.keys_s, n, cbits, c.dist_s);
     SoaRows rows;
     for (int j = 0; j < c.nrep[cc]; ++j) {
       const int r = c.rep_idx[(size_t)cc * kMaxReps + j];
@@ -642,14 +743,28 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
       rows.f[j] = c.f_s + (size_t)r * n;
     }
     if (pack) {
-      hipLaunchKernelGGL(k_gather_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, idx_out,
-                         packed + (size_t)cc * n, n, c.nrep[cc], rows);
-      continue;
+      hipLaunchKernelGGL(k_gather_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s,
+                         b.idx_out, packed + (size_t)cc * n, n, c.nrep[cc], rows);
+      return 0;
     }
     const int64_t tiles = (n + kGatherTile - 1) / kGatherTile;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)ctx->n_cu * 8));
-    hipLaunchKernelGGL(k_gather_cond_tile, dim3(grid), dim3(256), 0, s, idx_out, c.d_raw,
-                       c.d_f, n, R, reps_c, c.nrep[cc], rows);
+    hipLaunchKernelGGL(k_gather_cond_tile, dim3(grid), dim3(256), 0, b.s, b.idx_out, c.d_raw,
+                       c.d_f, n, R, d_reps + cc * kMaxReps, c.nrep[cc], rows);
+    return 0;
+  };
+  key_pass(0, main);
+  if (two) {
+    // the fork: the side stream starts behind k_iota, the design uploads and
+    // the (first) key pass; c.join_prep() brings it back
+    HIP_TRY(hipEventRecord(ctx->prep_fork, s));
+    HIP_TRY(hipStreamWaitEvent(ctx->prep_side, ctx->prep_fork, 0));
+    c.forked = true;
+  }
+  if (int rc = sort_gather(0, main)) return rc;
+  for (int cc = 1; cc < C; ++cc) {
+    key_pass(cc, side);
+    if (int rc = sort_gather(cc, side)) return rc;
   }
   return 0;
 }
@@ -660,7 +775,16 @@ int sort_and_gather(DispCall& c) {
   h3d_ctx* ctx = c.ctx;
   const int64_t n = c.n;
   const int R = c.R, D = c.D;
-  ProfScope ps(ctx, "disp_prep", n);
+  // disp_prep ends with this stage; a forked prep's side branch may run on
+  // under the table kernels, and the scope stays open until it has joined
+  // (start_qcml): it measures the critical path on the call's stream
+  c.prep_scope.emplace(ctx, "disp_prep", n);
+  struct ScopeEnd {
+    DispCall& c;
+    ~ScopeEnd() {
+      if (!c.forked) c.prep_scope.reset();
+    }
+  } scope_end{c};
   Scratch sc{ctx};
   int32_t* idx_in = sc.get<int32_t>("idx_in", n);
   int32_t* idx_out = sc.get<int32_t>("idx_out_c", n);
@@ -853,6 +977,10 @@ int start_qcml(DispCall& c) {
   c.d_queue = sc.get<int>("brent_queue", 2);
   if (!sc.ok) return fail(H3D_ENOMEM, "brent queue");
   launch_seg_update(c, 1, 0);
+  // the join of a forked prep: k_disp_tables, the table upload, the gang
+  // setup and the list above need only the segment bounds; the equalize pass
+  // that comes next reads every condition's rows
+  c.join_prep();
   if (!ctx->h_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_meta, 32, hipHostMallocDefault));
   c.h_meta = ctx->h_meta;
   const size_t res_bytes = (size_t)c.S * 8 + (size_t)c.S * sizeof(SegState) + 8;
@@ -1146,6 +1274,7 @@ h3d_ctx* h3d_open(int device) {
   if (const char* e = std::getenv("H3D_BRENT")) ctx->brent_gang = std::atoi(e);
   if (const char* e = std::getenv("H3D_BRENT_LDS_KB")) ctx->brent_lds_kb = std::atoi(e);
   if (const char* e = std::getenv("H3D_NLL_FULL")) ctx->nll_full = std::atoi(e);
+  if (const char* e = std::getenv("H3D_PREP_STREAMS")) ctx->prep_streams = std::atoi(e);
   if (const char* e = std::getenv("H3D_GANG_P")) ctx->gang_px = std::atoi(e);
   if (hipMalloc((void**)&ctx->work_count, 2 * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(ctx->work_count, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {
@@ -1154,6 +1283,12 @@ h3d_ctx* h3d_open(int device) {
     fail(H3D_ENOMEM, "counter allocation failed");
     return nullptr;
   }
+  // The prep's side stream, now rather than with the first fork: HIP maps
+  // streams onto a few hardware queues, a stream created once they are all
+  // taken shares one, and two streams on one queue run in enqueue order.
+  // Created lazily it shared the benchmark's queue with the call's stream
+  // (no overlap); a stream that cannot be had now is tried again by the call.
+  if (ctx->prep_streams == 2) (void)prep_side_ready(ctx);
   return ctx;
 }
 
@@ -1161,6 +1296,7 @@ void h3d_close(h3d_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->prep_side) (void)hipStreamSynchronize(ctx->prep_side);
   prof_collect(ctx);
   for (auto& kv : ctx->bufs)
     if (kv.second.first) (void)hipFree(kv.second.first);
@@ -1169,6 +1305,9 @@ void h3d_close(h3d_ctx* ctx) {
   if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
   if (ctx->h_stage_done) (void)hipEventDestroy(ctx->h_stage_done);
   if (ctx->bounce_ev) (void)hipEventDestroy(ctx->bounce_ev);
+  if (ctx->prep_fork) (void)hipEventDestroy(ctx->prep_fork);
+  if (ctx->prep_join) (void)hipEventDestroy(ctx->prep_join);
+  if (ctx->prep_side) (void)hipStreamDestroy(ctx->prep_side);
   if (ctx->own) (void)hipStreamDestroy(ctx->own);
   delete ctx;  // (the PinnedBufs free themselves)
 }

@@ -148,6 +148,17 @@ struct h3d_ctx {
   // kernels (the replicate count a constant, predicate-free Brent trips; the
   // same bits); 0 = always the general ones
   int nll_full = 1;
+  // H3D_PREP_STREAMS: 2 = estimate_disp's prep sorts and gathers conditions
+  // 1 .. C-1 on prep_side while condition 0's chain and the table kernels
+  // run on `stream` (fork / join through the two events; a
+  // call too large to gain from it stays on `stream`, sort_by_condition);
+  // 1 = everything on `stream`, one condition after the other
+  int prep_streams = 2;
+  // created by h3d_open with the switch at 2 (early: a stream created when
+  // the process's hardware queues are all taken shares one, and two streams
+  // on one queue run in enqueue order), destroyed with the ctx
+  hipStream_t prep_side = nullptr;
+  hipEvent_t prep_fork = nullptr, prep_join = nullptr;
   double qcml_tol = 1e-4;  // h3d_set_qcml_tol (qcml's tol, dispersion.py:10)
   // gang Brent slice (pixels; 0 = sized from the call, gang_setup_dev)
   int gang_px = 0;
