@@ -262,7 +262,8 @@ void launch_brent(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t* seg_
   if (!queue_zeroed) (void)hipMemsetAsync(queue, 0, sizeof(int), ctx->stream);
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBrentBlock), lds_px ? lds_px * 8 * M : 0,
                      ctx->stream, pd, n, seg_start, S, C, rep_idx, n_rep, st, seg_flags,
-                     result, queue, ctx->work_count, lds_px, gate_meta, live_min, gang_abort);
+                     result, queue, ctx->work_count, lds_px, gate_meta, live_min, gang_abort,
+                     ctx->nll_ranges);
 #ifdef H3D_BRENT_CLOCK
   unsigned long long clk[38];
   (void)hipMemcpyFromSymbolAsync(clk, HIP_SYMBOL(g_brent_clk), sizeof(clk), 0,
@@ -423,7 +424,8 @@ void launch_brent_gang(h3d_ctx* ctx, const double* pd, int64_t n, const int64_t*
   hipLaunchKernelGGL(k, dim3(grid), dim3(kGangThreads), 0, ctx->stream, pd,
                      n, seg_start, S, C, rep_idx, n_rep, st, seg_flags, result, queue,
                      g.task_seg, g.task_g, g.T, g.P, g.part, g.tag, g.gmax, g.abort,
-                     g.timeout, ctx->work_count, epoch, gate_meta, live_max);
+                     g.timeout, ctx->work_count, epoch, gate_meta, live_max,
+                     ctx->nll_ranges);
 }
 
 // algorithmic HBM bytes of the disp_work launches so far: an equalize
@@ -1274,6 +1276,7 @@ h3d_ctx* h3d_open(int device) {
   if (const char* e = std::getenv("H3D_BRENT")) ctx->brent_gang = std::atoi(e);
   if (const char* e = std::getenv("H3D_BRENT_LDS_KB")) ctx->brent_lds_kb = std::atoi(e);
   if (const char* e = std::getenv("H3D_NLL_FULL")) ctx->nll_full = std::atoi(e);
+  if (const char* e = std::getenv("H3D_NLL_RANGES")) ctx->nll_ranges = std::atoi(e);
   if (const char* e = std::getenv("H3D_PREP_STREAMS")) ctx->prep_streams = std::atoi(e);
   if (const char* e = std::getenv("H3D_GANG_P")) ctx->gang_px = std::atoi(e);
   if (hipMalloc((void**)&ctx->work_count, 2 * sizeof(unsigned long long)) != hipSuccess ||

@@ -148,6 +148,10 @@ struct h3d_ctx {
   // kernels (the replicate count a constant, predicate-free Brent trips; the
   // same bits); 0 = always the general ones
   int nll_full = 1;
+  // H3D_NLL_RANGES: the Brent kernels take the r >= 5 form of the NLL term
+  // (nll_pixel_r5, h3d_model.h nll_mode) for the evaluations it covers (the
+  // same bits); 0 = the large / mid / general dispatch only
+  int nll_ranges = 1;
   // H3D_PREP_STREAMS: 2 = estimate_disp's prep sorts and gathers conditions
   // 1 .. C-1 on prep_side while condition 0's chain and the table kernels
   // run on `stream` (fork / join through the two events; a

@@ -29,6 +29,7 @@ extern "C" {
 H3DT_UNARY(lgam, lgam)
 H3DT_UNARY(lgam_nll, lgam_nll)
 H3DT_UNARY(log_fast, log_fast)
+H3DT_UNARY(log_fast_fp_index, log_fast_fp_index)
 H3DT_UNARY(ndtr, ndtr)
 H3DT_UNARY(ndtri, ndtri)
 H3DT_UNARY(log1pmx, log1pmx)
@@ -38,6 +39,17 @@ H3DT_BINARY(igamc, igamc)
 H3DT_BINARY(igami, igami)
 H3DT_BINARY(igamci, igamci)
 H3DT_BINARY(chi2_sf, chi2_sf)
+
+// log_fast's table bucket of frexp(x)'s mantissa: from its bits (the form in
+// use) and by the FP64 expression it replaced
+void h3dt_log_index(int64_t n, const double* x, int32_t* bits, int32_t* fp) {
+  for (int64_t i = 0; i < n; ++i) {
+    int e;
+    const double m = frexp(x[i], &e);
+    bits[i] = h3d::log_fast_index(m);
+    fp[i] = h3d::log_fast_index_fp(m);
+  }
+}
 
 // fit_mu_hat per pixel: x (n, r) int32, b (n, r), alpha (n, r) -> mu (n)
 int h3dt_fit_mu(int64_t n, int r, const int32_t* x, const double* b,
@@ -83,15 +95,18 @@ int h3dt_equalize(int64_t n, int r, const int32_t* x, const double* f,
 }
 
 // per-pixel NLL terms at delta by the general / mid (r >= 10) / large
-// (r >= 20) forms of the Brent kernels (mode 0 / 1 / 2)
+// (r >= 20) forms of the Brent kernels (mode 0 / 1 / 2), and their r >= 5 /
+// n r >= 5 forms (mode 3 / 4)
 int h3dt_nll_terms(int64_t n, int r, const double* pseudo, double delta, int mode,
                    double* out) {
-  if (r < 1 || r > M || mode < 0 || mode > 2) return -1;
+  if (r < 1 || r > M || mode < 0 || mode > 4) return -1;
   const h3d::NllConst kc = h3d::nll_const(delta, r);
   for (int64_t i = 0; i < n; ++i) {
     double ps[M];
     for (int k = 0; k < M; ++k) ps[k] = k < r ? pseudo[i * r + k] : 0.0;
-    out[i] = mode == 2   ? h3d::nll_pixel_large<M>(ps, r, kc)
+    out[i] = mode == 4   ? h3d::nll_pixel_nr5<M>(ps, r, kc)
+             : mode == 3 ? h3d::nll_pixel_r5<M>(ps, r, kc)
+             : mode == 2 ? h3d::nll_pixel_large<M>(ps, r, kc)
              : mode == 1 ? h3d::nll_pixel_mid<M>(ps, r, kc)
                          : h3d::nll_pixel<M>(ps, r, kc);
   }

@@ -817,8 +817,9 @@ static __device__ __noinline__ void seg_step_ool(SegState* s, double total, int 
 // waves/SIMD); the terms still join the sum in pixel order (M >= 8: one
 // pixel per trip -- the pair spilled at the 128-VGPR budget of
 // __launch_bounds__(512, 4)). MODE 2: every argument >= kNllLargeR
-// (nll_pixel_large); 1: >= kNllMidR (nll_pixel_mid); 0: nll_pixel.
-// (nll_pixel_large).
+// (nll_pixel_large); 1: >= kNllMidR (nll_pixel_mid); 3: r >= kNllR5
+// (nll_pixel_r5); 4: n r >= kNllNr5 (nll_pixel_nr5); 0: nll_pixel. The
+// evaluation's mode is nll_mode's (h3d_model.h).
 #ifndef H3D_BRENT_PAIR2
 #define H3D_BRENT_PAIR2 2
 #endif
@@ -869,6 +870,8 @@ __device__ __forceinline__ double brent_segment_sum(
   auto term = [&](const double* v) {
     if constexpr (MODE == 2) return nll_pixel_large<M>(v, nr, kc, s_tab);
     else if constexpr (MODE == 1) return nll_pixel_mid<M>(v, nr, kc, s_tab);
+    else if constexpr (MODE == 3) return nll_pixel_r5<M>(v, nr, kc, s_tab);
+    else if constexpr (MODE == 4) return nll_pixel_nr5<M>(v, nr, kc, s_tab);
     else return nll_pixel<M>(v, nr, kc, s_tab);
   };
   for (int64_t i = threadIdx.x; i < el - b; i += kPair * kBlockT) {
@@ -981,6 +984,8 @@ __device__ __forceinline__ double brent_segment_sum_full(
   auto term = [&](const double* v) {
     if constexpr (MODE == 2) return nll_pixel_large<M>(v, M, kc, s_tab);
     else if constexpr (MODE == 1) return nll_pixel_mid<M>(v, M, kc, s_tab);
+    else if constexpr (MODE == 3) return nll_pixel_r5<M>(v, M, kc, s_tab);
+    else if constexpr (MODE == 4) return nll_pixel_nr5<M>(v, M, kc, s_tab);
     else return nll_pixel<M>(v, M, kc, s_tab);
   };
   // a thread's full trips over `len` pixels, its first at threadIdx.x
@@ -1067,6 +1072,20 @@ __device__ __forceinline__ double brent_segment_sum_full(
   return acc;
 }
 
+// one evaluation's sum by its mode (nll_mode: the same for every thread of
+// the segment, made wave-uniform here): sum(integral_constant<int, MODE>)
+template <typename F>
+__device__ __forceinline__ double brent_sum_by_mode(int mode, F&& sum) {
+  using std::integral_constant;
+  const int md = __builtin_amdgcn_readfirstlane(mode);
+  if (md == 2) return sum(integral_constant<int, 2>{});
+  if (md == 1) return sum(integral_constant<int, 1>{});
+  if (md == 3) return sum(integral_constant<int, 3>{});
+  if constexpr (H3D_NLL_FORM4 != 0)
+    if (md == 4) return sum(integral_constant<int, 4>{});
+  return sum(integral_constant<int, 0>{});
+}
+
 // The segment's first `lds_px` pixels are staged in LDS once per search (the
 // dynamic shared buffer, up to ~150 KB: one 1024-thread workgroup per CU);
 // every evaluation reads them from there and streams only the rest -- the
@@ -1101,7 +1120,7 @@ __global__ __launch_bounds__(brent_block<M>(), M >= 16 ? 2 : 4) void k_brent(
     const int* __restrict__ seg_flags, double* __restrict__ result,
     int* __restrict__ queue, unsigned long long* __restrict__ work_count,
     int64_t lds_px, const int32_t* __restrict__ gate_meta, int live_min,
-    const int* __restrict__ gang_abort) {
+    const int* __restrict__ gang_abort, int nll_ranges) {
   extern __shared__ double s_pd[];  // [nr][lds_px]
   // gate (device-side choice between this kernel and k_brent_gang, both
   // launched): run when the live segments fill the chip, or when a gang
@@ -1159,20 +1178,14 @@ __global__ __launch_bounds__(brent_block<M>(), M >= 16 ? 2 : 4) void k_brent(
       // paths (nll_pixel_large / _mid), the same for every thread of the
       // segment
       constexpr bool kPr = H3D_BRENT_PRIO != 0;
-      double acc;
-      if constexpr (kFull) {
-        acc = (kc.r >= kNllLargeR)
-            ? brent_segment_sum_full<M, kBrentBlock, 2, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab)
-            : (kc.r >= kNllMidR)
-            ? brent_segment_sum_full<M, kBrentBlock, 1, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab)
-            : brent_segment_sum_full<M, kBrentBlock, 0, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab);
-      } else {
-        acc = (kc.r >= kNllLargeR)
-            ? brent_segment_sum<M, kBrentBlock, 2, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab)
-            : (kc.r >= kNllMidR)
-            ? brent_segment_sum<M, kBrentBlock, 1, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab)
-            : brent_segment_sum<M, kBrentBlock, 0, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab);
-      }
+      auto sum = [&](auto mode) {
+        constexpr int kMode = decltype(mode)::value;
+        if constexpr (kFull)
+          return brent_segment_sum_full<M, kBrentBlock, kMode, kPr>(s_pd, lds_px, pd, n, ri, b, el, e, kc, s_tab);
+        else
+          return brent_segment_sum<M, kBrentBlock, kMode, kPr>(s_pd, lds_px, pd, n, ri, nr, b, el, e, kc, s_tab);
+      };
+      const double acc = brent_sum_by_mode(nll_mode(kc, nr, nll_ranges != 0), sum);
       double wacc = acc;
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) wacc += __shfl_xor(wacc, off, 64);
@@ -1288,7 +1301,7 @@ __global__ __launch_bounds__(kGangThreads, (kFull ? 4 : 0)) void k_brent_gang(
     double* __restrict__ part /* 2 x S x gmax */, int* __restrict__ tag /* 2 x S x gmax */,
     int gmax, int* __restrict__ abort_flag, long long timeout,
     unsigned long long* __restrict__ work_count, int epoch,
-    const int32_t* __restrict__ gate_meta, int live_max) {
+    const int32_t* __restrict__ gate_meta, int live_max, int nll_ranges) {
   // gate (device-side choice, see k_brent): run while the live segments
   // leave CUs idle, unless a gang has aborted
   if (gate_meta && (gate_meta[3] >= live_max || *abort_flag)) return;
@@ -1331,20 +1344,14 @@ __global__ __launch_bounds__(kGangThreads, (kFull ? 4 : 0)) void k_brent_gang(
       const NllConst kc = s_st.k;
       // the slice (no LDS head), two pixels per trip for M <= 4, as k_brent
       // (the progress priority of k_brent measured neutral here, r06z)
-      double acc;
-      if constexpr (kFull) {
-        acc = (kc.r >= kNllLargeR)
-            ? brent_segment_sum_full<M, kGangThreads, 2>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab)
-            : (kc.r >= kNllMidR)
-            ? brent_segment_sum_full<M, kGangThreads, 1>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab)
-            : brent_segment_sum_full<M, kGangThreads, 0>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab);
-      } else {
-        acc = (kc.r >= kNllLargeR)
-            ? brent_segment_sum<M, kGangThreads, 2>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab)
-            : (kc.r >= kNllMidR)
-            ? brent_segment_sum<M, kGangThreads, 1>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab)
-            : brent_segment_sum<M, kGangThreads, 0>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab);
-      }
+      auto sum = [&](auto mode) {
+        constexpr int kMode = decltype(mode)::value;
+        if constexpr (kFull)
+          return brent_segment_sum_full<M, kGangThreads, kMode>(nullptr, 0, pd, n, ri, sb, sb, se, kc, s_tab);
+        else
+          return brent_segment_sum<M, kGangThreads, kMode>(nullptr, 0, pd, n, ri, nr, sb, sb, se, kc, s_tab);
+      };
+      double acc = brent_sum_by_mode(nll_mode(kc, nr, nll_ranges != 0), sum);
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
       if (lane == 0) wpart[wid] = acc;

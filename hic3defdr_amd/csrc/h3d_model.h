@@ -556,6 +556,84 @@ H3D_HD double nll_pixel_mid(const double* d, int n, const NllConst& k,
 }
 constexpr double kNllMidR = 10.0;
 
+// Two more forms for trial points whose r is uniform but below kNllMidR
+// (round 11; conditions of two or more replicates, H3D_NLL_RANGES). Every
+// bounded search opens at r = 1.64, 0.63, 3.28, 5.92 (tools/brent_points.py),
+// and the general form computes both rise5(x) and rise5(x + 5) for every
+// lgamma and selects per lane. Each form below computes only what
+// nll_pixel's selects would have picked there, so the same bits.
+//
+// r >= kNllR5 (and so n r >= 10): every replicate argument d + r is >= 5 --
+// one shift at most, per lane -- and z + n r >= 10 takes no shift: its
+// product is 1 and nll_pixel's prod * recip_nll(1) is prod (recip_nll(1) is
+// exactly 1: the Newton step rounds 1 - eps^2 to 1 for any v_rcp_f64 within
+// an ulp).
+constexpr double kNllR5 = 5.0;
+template <int M>
+H3D_HD double nll_pixel_r5(const double* d, int n, const NllConst& k,
+                           const LogTab* tab = kLogTab) {
+  double lg[M];
+  double lnp = 0.0, prod = 1.0;
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double pj = 1.0;
+    lg[j] = (j < n) ? lgam_nll_parts_ge5(d[j] + k.r, &pj, tab) : 0.0;
+    prod *= pj;
+    if ((j & 7) == 7 && j + 1 < M) {  // keep 8 factors per logarithm
+      lnp += log_fast(prod, tab);
+      prod = 1.0;
+    }
+  }
+  const double z = np_sum<M>(d, n);
+  const double lz = lgam_nll_mid(z + k.nr, tab);
+  lnp += log_fast(prod, tab);
+  return np_sum<M>(lg, n) - lnp + k.lg_nr - lz - k.n_lg_r;
+}
+
+// n r >= kNllNr5: z + n r >= 5 takes one shift at most; the replicate
+// lgammas are nll_pixel's. The Brent kernels are built without this form
+// (H3D_NLL_FORM4 = 0): it takes 11 of the general trip's 383 VALU
+// instructions off one evaluation in twelve, and with its loops
+// k_brent<2, true> spilled a register pair (16 B of scratch, none without;
+// DESIGN.md §5 round 11). The test ABI keeps it (h3dt_nll_terms mode 4).
+constexpr double kNllNr5 = 5.0;
+#ifndef H3D_NLL_FORM4
+#define H3D_NLL_FORM4 0
+#endif
+template <int M>
+H3D_HD double nll_pixel_nr5(const double* d, int n, const NllConst& k,
+                            const LogTab* tab = kLogTab) {
+  double lg[M];
+  double lnp = 0.0, prod = 1.0;
+#pragma unroll
+  for (int j = 0; j < M; ++j) {
+    double pj = 1.0;
+    lg[j] = (j < n) ? lgam_nll_parts(d[j] + k.r, &pj, tab) : 0.0;
+    prod *= pj;
+    if ((j & 7) == 7 && j + 1 < M) {  // keep 8 factors per logarithm
+      lnp += log_fast(prod, tab);
+      prod = 1.0;
+    }
+  }
+  const double z = np_sum<M>(d, n);
+  double pz = 1.0;
+  const double lz = lgam_nll_parts_ge5(z + k.nr, &pz, tab);
+  lnp += log_fast(prod * recip_nll(pz), tab);
+  return np_sum<M>(lg, n) - lnp + k.lg_nr - lz - k.n_lg_r;
+}
+
+// the form of an evaluation (the MODE of brent_segment_sum*): uniform over
+// the segment. ranges = 0: the dispatch before round 11 (modes 0..2).
+H3D_HD int nll_mode(const NllConst& k, int n, bool ranges) {
+  if (k.r >= kNllLargeR) return 2;
+  if (k.r >= kNllMidR) return 1;
+  if (ranges && n >= 2) {
+    if (k.r >= kNllR5 && k.nr >= 10.0) return 3;
+    if (H3D_NLL_FORM4 && k.nr >= kNllNr5) return 4;
+  }
+  return 0;
+}
+
 template <int M>
 H3D_HD double nll_pixel(const double* d, int n, const NllConst& k,
                         const LogTab* tab = kLogTab) {

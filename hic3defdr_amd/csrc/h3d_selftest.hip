@@ -28,7 +28,7 @@ constexpr int kBlock = 256;
 
 enum Op {
   kLgam, kLgamNll, kLogFast, kNdtr, kNdtri, kLog1pmx, kLgam1p,
-  kIgam, kIgamc, kIgami, kIgamci, kChi2Sf
+  kIgam, kIgamc, kIgami, kIgamci, kChi2Sf, kLogFastFp
 };
 
 template <int OP>
@@ -36,6 +36,7 @@ __device__ double unary_op(double x) {
   if constexpr (OP == kLgam) return h3d::lgam(x);
   else if constexpr (OP == kLgamNll) return h3d::lgam_nll(x);
   else if constexpr (OP == kLogFast) return h3d::log_fast(x);
+  else if constexpr (OP == kLogFastFp) return h3d::log_fast_fp_index(x);
   else if constexpr (OP == kNdtr) return h3d::ndtr(x);
   else if constexpr (OP == kNdtri) return h3d::ndtri(x);
   else if constexpr (OP == kLog1pmx) return h3d::log1pmx(x);
@@ -65,6 +66,17 @@ __global__ void k_binary(int64_t n, const double* __restrict__ a,
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     out[i] = binary_op<OP>(a[i], x[i]);
+}
+
+__global__ void k_log_index(int64_t n, const double* __restrict__ x,
+                            int32_t* __restrict__ bits, int32_t* __restrict__ fp) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int e;
+    const double m = frexp(x[i], &e);
+    bits[i] = h3d::log_fast_index(m);
+    fp[i] = h3d::log_fast_index_fp(m);
+  }
 }
 
 __global__ void k_fit_mu(int64_t n, int r, const int32_t* __restrict__ x,
@@ -139,7 +151,9 @@ __global__ void k_nll_terms(int64_t n, int r, const double* __restrict__ pseudo,
     double ps[M];
 #pragma unroll
     for (int k = 0; k < M; ++k) ps[k] = (k < r) ? pseudo[i * r + k] : 0.0;
-    out[i] = mode == 2   ? h3d::nll_pixel_large<M>(ps, r, kc)
+    out[i] = mode == 4   ? h3d::nll_pixel_nr5<M>(ps, r, kc)
+             : mode == 3 ? h3d::nll_pixel_r5<M>(ps, r, kc)
+             : mode == 2 ? h3d::nll_pixel_large<M>(ps, r, kc)
              : mode == 1 ? h3d::nll_pixel_mid<M>(ps, r, kc)
                          : h3d::nll_pixel<M>(ps, r, kc);
   }
@@ -262,6 +276,7 @@ int h3dt_device_ok(void) {
 H3DT_UNARY(lgam, kLgam)
 H3DT_UNARY(lgam_nll, kLgamNll)
 H3DT_UNARY(log_fast, kLogFast)
+H3DT_UNARY(log_fast_fp_index, kLogFastFp)
 H3DT_UNARY(ndtr, kNdtr)
 H3DT_UNARY(ndtri, kNdtri)
 H3DT_UNARY(log1pmx, kLog1pmx)
@@ -271,6 +286,18 @@ H3DT_BINARY(igamc, kIgamc)
 H3DT_BINARY(igami, kIgami)
 H3DT_BINARY(igamci, kIgamci)
 H3DT_BINARY(chi2_sf, kChi2Sf)
+
+void h3dt_log_index(int64_t n, const double* x, int32_t* bits, int32_t* fp) {
+  Dev<double> dx(x, n);
+  Dev<int32_t> db(nullptr, n), df(nullptr, n);
+  hipLaunchKernelGGL(k_log_index, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, dx.p, db.p, df.p);
+  if (sync_ok()) {
+    db.to_host(bits);
+    df.to_host(fp);
+  }
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) bits[i] = fp[i] = -1;
+}
 
 int h3dt_fit_mu(int64_t n, int r, const int32_t* x, const double* b,
                 const double* alpha, double* mu) {
@@ -314,7 +341,7 @@ int h3dt_equalize(int64_t n, int r, const int32_t* x, const double* f,
 
 int h3dt_nll_terms(int64_t n, int r, const double* pseudo, double delta, int mode,
                    double* out) {
-  if (r < 1 || r > M || mode < 0 || mode > 2) return -1;
+  if (r < 1 || r > M || mode < 0 || mode > 4) return -1;
   Dev<double> dp(pseudo, n * r), dout_(nullptr, n);
   const h3d::NllConst kc = h3d::nll_const(delta, r);
   hipLaunchKernelGGL(k_nll_terms, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, r, dp.p, kc, mode,

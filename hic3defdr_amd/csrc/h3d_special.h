@@ -18,6 +18,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
 // FMA contraction off for everything built on these headers: it keeps the
 // device arithmetic op-for-op with the host test build (g++
@@ -212,6 +213,10 @@ H3D_HD double div_fast(double a, double b) {
 #ifndef H3D_HFMA_ASM
 #define H3D_HFMA_ASM 1
 #endif
+// exp_fast's wave-uniform in-range path (round 11; 0 = always the selects)
+#ifndef H3D_EXP_UNIFORM
+#define H3D_EXP_UNIFORM 1
+#endif
 H3D_HD double hfma(double p, double x, double c) {
 #if defined(__HIP_DEVICE_COMPILE__) && H3D_HFMA_ASM
   double r;
@@ -245,11 +250,37 @@ struct LogTab {
 // takes two fma off every log. Used by the NLL sums (finite x > 0 by
 // construction) and, through log_fast_checked, the incomplete-gamma
 // prefactor.
-// (tab: the table's copy to read -- kLogTab, or a kernel's copy in LDS)
-H3D_HD double log_fast(double x, const LogTab* tab = kLogTab) {
+//
+// The bucket i = round(1024 (m - 1/2)) comes from m's bits (round 11): with
+// m = (1 + f) / 2 and b the top ten bits of the fraction f, 1024 (m - 1/2) =
+// b / 2 + rho, rho in [0, 1/2) the lower 42 bits' share, so the rounded value
+// is b / 2 for even b and (b + 1) / 2 for odd b: i = (b + 1) >> 1. The FP64
+// expression it replaces (log_fast_index_fp: every step of it exact, so the
+// same integer) was five dependent instructions between frexp and the table
+// read on gfx950 (add, ldexp, add, cvt, shift), this is three integer ones.
+// frexp has normalised m, so subnormal x is covered.
+H3D_HD int log_fast_index(double m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const unsigned hi = (unsigned)__double2hiint(m);
+#else
+  unsigned long long u;
+  memcpy(&u, &m, sizeof u);
+  const unsigned hi = (unsigned)(u >> 32);
+#endif
+  return (int)((((hi >> 10) & 0x3ffu) + 1u) >> 1);  // 0..512
+}
+// the index as it was computed before (tests only: test_log_index_bits.py)
+H3D_HD int log_fast_index_fp(double m) {
+  return (int)((m - 0.5) * (double)kLogTabSteps + 0.5);
+}
+
+// (tab: the table's copy to read -- kLogTab, or a kernel's copy in LDS;
+// kFpIndex: the bucket by log_fast_index_fp, tests only)
+template <bool kFpIndex = false>
+H3D_HD double log_fast_t(double x, const LogTab* tab) {
   int e;
   const double m = frexp(x, &e);  // [0.5, 1)
-  const int i = (int)((m - 0.5) * (double)kLogTabSteps + 0.5);  // 0..512
+  const int i = kFpIndex ? log_fast_index_fp(m) : log_fast_index(m);
   const LogTab tb = tab[i];
   const double t = fma(m, tb.c, -1.0);
   double q = 1.0 / 5.0;
@@ -260,6 +291,9 @@ H3D_HD double log_fast(double x, const LogTab* tab = kLogTab) {
   const double de = (double)(e - (i <= kLogTabShifted ? 1 : 0));
   return de * 6.93147180369123816490e-01 + (de * 1.90821492927058770002e-10 + (tb.l + lp));
 }
+H3D_HD double log_fast(double x, const LogTab* tab = kLogTab) { return log_fast_t<false>(x, tab); }
+// log_fast with the FP64 bucket expression (tests only)
+H3D_HD double log_fast_fp_index(double x) { return log_fast_t<true>(x, kLogTab); }
 
 // log_fast for any x: frexp of 0 / inf would index outside the table, so x
 // is first replaced by 1 there and libm's values (-inf, inf, NaN) are
@@ -290,6 +324,11 @@ H3D_HD double stirling_nll(double r2) {
 // (truncation < 5e-18 relative) in hfma steps with the coefficients in
 // SGPRs, scaled by ldexp; overflow / underflow / NaN as libm. ~1 ulp. OCML's
 // exp carried a v_mov_b64 copy of its constant per Horner step. Host: exp.
+// The clamp of k and the overflow / underflow / NaN selects (~10 of its ~29
+// VALU instructions) are skipped by a wave whose active lanes all have |x| <
+// 700 (one ballot; the selects would have kept ldexp(p, k) in every lane, so
+// the same bits). Measured (tools/ab_lib.sh, cfg2, round 11): equalize
+// 2.42-2.44 -> 2.38-2.39 ms per step.
 H3D_HD double exp_fast(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double kd = rint(x * 1.44269504088896338700e+00);
@@ -326,6 +365,12 @@ H3D_HD double exp_fast(double x) {
   p = hfma(p, r, 0.5);
   p = hfma(p, r, 1.0);
   p = hfma(p, r, 1.0);
+#endif
+#if H3D_EXP_UNIFORM
+  // a wave whose active lanes are all finite and inside (-700, 700): the
+  // clamp and the three selects below would pick ldexp(p, kd) in every lane
+  // (one wave-uniform test instead of them)
+  if (__builtin_amdgcn_ballot_w64(!(fabs(x) < 700.0)) == 0) return ldexp(p, (int)kd);
 #endif
   const int k = (int)fmax(fmin(kd, 1100.0), -1100.0);
   double v = ldexp(p, k);
@@ -432,6 +477,25 @@ H3D_HD double lgam_nll_parts(double x, double* P, const LogTab* tab = kLogTab) {
     const double px = rise5(x);
     p = two ? px * pu : pu;
     y = u + 5.0;
+  }
+  *P = p;
+  const double r = recip_nll(y), r2 = r * r;
+  const double corr = r * stirling_nll(r2);
+  return (y - 0.5) * log_fast(y, tab) - y + kLogSqrt2Pi + corr;
+}
+
+// lgam_nll_parts for x >= 5 (the caller knows it for every lane): the shift
+// is one rise5 step at most, so the second product and the selects of the
+// double shift are not computed -- the values lgam_nll_parts selects there
+// (its u is x, its p is rise5(x), its y is x + 5)
+H3D_HD double lgam_nll_parts_ge5(double x, double* P, const LogTab* tab = kLogTab) {
+#if defined(__clang__)
+#pragma clang fp contract(fast)
+#endif
+  double y = x, p = 1.0;
+  if (x < 10.0) {
+    p = rise5(x);
+    y = x + 5.0;
   }
   *P = p;
   const double r = recip_nll(y), r2 = r * r;
