@@ -36,6 +36,7 @@ EXPORTS = [
     'h3d_disp_pixels_dev', 'h3d_table_gather_dev', 'h3d_disp_seg_stats',
     'h3d_scale_disp_dev', 'h3d_npz_backend', 'h3d_npz_csr_read_slack',
     'h3d_pixel_f_dev', 'h3d_read_text_column', 'h3d_set_qcml_tol',
+    'h3d_window_gather', 'h3d_window_gather_dev', 'h3d_stack_aggregate',
 ]
 
 
@@ -162,6 +163,13 @@ def load_library(path=None):
                                             _P, _P, _I64, _P]),
             'h3d_npz_csr_read': (_I, [ctypes.c_char_p, _I64, _I64, _P, _P, _P,
                                       _P]),
+            'h3d_window_gather': (_I, [_P, _P, _P, _P, _P, _I64, _I, _I, _I,
+                                       _P, _I, _P, _I64, _I, _I, _I, _I, _D,
+                                       _P]),
+            'h3d_window_gather_dev': (_I, [_P, _P, _P, _P, _P, _I64, _I, _I,
+                                           _I, _P, _I, _P, _I64, _I, _I, _I,
+                                           _I, _D, _P]),
+            'h3d_stack_aggregate': (_I, [_P, _P, _I64, _I, _I, _P, _P]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -686,6 +694,77 @@ class Context(object):
             self.handle, _ptr(data), _ptr(f), n, R, C, _ptr(cond),
             float(min_disp), _ptr(out)), 'h3d_mme_per_pixel')
         return out
+
+    # -- dense views (get_matrix / select_matrix / APA) ----------------------
+    def window_gather(self, indices, data, origins, h, w, shape, indptr=None,
+                      row=None, cols=None, symmetrize=False, mean=False,
+                      fill=np.nan):
+        """W dense h x w windows of a CSR matrix ``shape`` = (n_rows, n_cols)
+        in one launch (h3d_window_gather): ``indices`` (nnz), ``data`` (nnz,)
+        or (nnz, ld), and either ``indptr`` or the sorted ``row`` (nnz) of a
+        lexsorted table; ``origins`` (W, 2) int32 window corners (a row0 of
+        INT32_MIN: an all-NaN window); ``cols`` the data columns taken
+        (default: all). Returns (K, W, h, w), or (W, h, w) with ``mean``."""
+        if (indptr is None) == (row is None):
+            raise ValueError('pass exactly one of indptr and row')
+        indices = _c(indices, np.int32)
+        data = _c(data, np.float64)
+        if data.ndim == 1:
+            data = data.reshape(-1, 1)
+        nnz, ld = data.shape
+        if data.ndim != 2 or len(indices) != nnz:
+            raise ValueError('data must be (nnz,) or (nnz, ld), indices (nnz,)')
+        n_rows, n_cols = int(shape[0]), int(shape[1])
+        if indptr is not None:
+            indptr = _c(indptr, np.int64)
+            if len(indptr) != n_rows + 1:
+                raise ValueError('indptr must have n_rows + 1 entries')
+        else:
+            row = _c(row, np.int32)
+            if len(row) != nnz:
+                raise ValueError('row must have nnz entries')
+        cols = _c(np.arange(ld) if cols is None else cols, np.int32)
+        origins = _c(origins, np.int32).reshape(-1, 2)
+        W, K = len(origins), len(cols)
+        # (an output the library refuses for its size is not allocated)
+        out = np.empty((W, h, w) if mean else (K, W, h, w), dtype=np.float64) \
+            if K * W * int(h) * int(w) < 2 ** 31 else None
+        _check(self.lib.h3d_window_gather(
+            self.handle, _ptr(indptr), _ptr(row), _ptr(indices), _ptr(data),
+            nnz, ld, n_rows, n_cols, _ptr(cols), K, _ptr(origins), W, int(h),
+            int(w), int(bool(symmetrize)), int(bool(mean)), float(fill),
+            _ptr(out)), 'h3d_window_gather')
+        return out
+
+    def window_gather_dev(self, d_indices, d_data, nnz, ld, shape, cols,
+                          d_origins, W, h, w, d_out, d_indptr=None,
+                          d_row=None, symmetrize=False, mean=False,
+                          fill=np.nan):
+        """window_gather on device buffers (h3d_window_gather_dev); ``cols``
+        stays on the host. Synchronous."""
+        cols = _c(cols, np.int32)
+        _check(self.lib.h3d_window_gather_dev(
+            self.handle, _P(d_indptr) if d_indptr else None,
+            _P(d_row) if d_row else None, _P(d_indices), _P(d_data), nnz, ld,
+            int(shape[0]), int(shape[1]), _ptr(cols), len(cols),
+            _P(d_origins), W, int(h), int(w), int(bool(symmetrize)),
+            int(bool(mean)), float(fill), _P(d_out)),
+            'h3d_window_gather_dev')
+
+    def stack_aggregate(self, stack):
+        """(count int64, sum float64), each (h, w): per cell of a stack
+        (W, h, w) the windows that are not NaN there and their sum, in a
+        fixed order (h3d_stack_aggregate)."""
+        stack = _c(stack, np.float64)
+        if stack.ndim != 3:
+            raise ValueError('stack must be (W, h, w)')
+        W, h, w = stack.shape
+        count = np.empty((h, w), dtype=np.int64)
+        total = np.empty((h, w), dtype=np.float64)
+        _check(self.lib.h3d_stack_aggregate(self.handle, _ptr(stack), W, h, w,
+                                            _ptr(count), _ptr(total)),
+               'h3d_stack_aggregate')
+        return count, total
 
     # -- measurement ---------------------------------------------------------
     def profile(self, on=True, level=2):

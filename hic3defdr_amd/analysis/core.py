@@ -542,6 +542,85 @@ class CoreHiC3DeFDR(object):
             return
         self._save_npy(self._npy(name, chrom), data)
 
+    # -- dense views ----------------------------------------------------
+    # per-replicate stages the '_mean' suffix averages within a condition
+    _MEAN_STAGES = ('raw', 'scaled')
+
+    def _view_table(self, name, chrom, rep, cond):
+        """The COO table behind a dense view of stage ``name``: (row, col,
+        data, cols, mean). ``name`` + '_mean' averages the condition's
+        replicates, in design order, inside the gather (``mean`` True,
+        ``cols`` their columns of the (pixels, reps) ``data``)."""
+        if name.endswith('_mean'):
+            base = name[:-len('_mean')]
+            if base not in self._MEAN_STAGES:
+                raise ValueError('%s: only %s can be averaged over a '
+                                 "condition's replicates"
+                                 % (name, ' / '.join(self._MEAN_STAGES)))
+            if cond is None:
+                raise ValueError('%s needs cond' % name)
+            cols = np.flatnonzero(np.asarray(self.design[cond], dtype=bool))
+            if len(cols) == 0:
+                raise ValueError('condition %s has no replicates' % cond)
+            row, col, data = self.load_data(base, chrom, coo=True)
+            return row, col, data, cols, True
+        row, col, data = self.load_data(name, chrom, rep=rep, cond=cond,
+                                        coo=True)
+        if data.ndim != 1:
+            raise ValueError('stage %s has %d columns: pass rep or cond'
+                             % (name, data.shape[1]))
+        return row, col, data, None, False
+
+    def get_matrix(self, name, chrom, row_slice, col_slice, rep=None,
+                   cond=None):
+        """Reference ``core.py:255-291``: stage ``name`` of ``chrom`` as the
+        dense float64 matrix ``row_slice`` x ``col_slice`` selects, both
+        triangles filled, NaN where no pixel is stored
+        (``util.matrices.select_matrix`` on ``load_data(..., coo=True)``).
+        ``raw_mean`` / ``scaled_mean`` average the replicates of ``cond`` in
+        design order, in the same launch. (The reference removes the suffix
+        with ``name.strip('_mean')``, which strips characters; here it is
+        removed as a suffix.)"""
+        from hic3defdr_amd.util import matrices
+        origin, h, w = matrices.slice_window(row_slice, col_slice)
+        row, col, data, cols, mean = self._view_table(name, chrom, rep, cond)
+        if h == 0 or w == 0:
+            matrices.check_table(row, col)
+            return np.full((h, w), np.nan)
+        out = matrices.table_windows(row, col, data, origin, h, w, cols=cols,
+                                     symmetrize=True, mean=mean)
+        return out[0] if mean else out[0, 0]
+
+    def apa_stack(self, name, chrom, clusters, width, min_dist=None,
+                  rep=None, cond=None):
+        """The APA stack (clusters, width, width) of stage ``name`` of
+        ``chrom`` straight from the outdir: ``util.apa.make_apa_stack``'s
+        windows (centres, ``min_dist`` and edge filtering on the chromosome's
+        bin count; NaN slices for clusters it drops) over the stage's upper
+        triangle, 0 where no pixel is stored. ``rep`` / ``cond`` and the
+        '_mean' suffix as in ``get_matrix``. Not in the reference, whose
+        walkthrough rebuilds a scipy matrix first."""
+        from hic3defdr_amd.util import apa, matrices
+        width = apa.check_width(width)
+        row, col, data, cols, mean = self._view_table(name, chrom, rep, cond)
+        n_bins = self.load_bias(chrom).shape[0]
+        origins, _ = apa.apa_windows(clusters, width, n_bins, min_dist)
+        if len(origins) == 0:
+            matrices.check_table(row, col)
+            return np.zeros((0, width, width))
+        out = matrices.table_windows(row, col, data, origins, width, width,
+                                     cols=cols, n_bins=n_bins,
+                                     symmetrize=False, mean=mean, fill=0.0)
+        return out if mean else out[0]
+
+    @staticmethod
+    def apa_mean(stack):
+        """``(mean, count)`` over the windows of an APA stack
+        (``util.apa.apa_mean``: ``np.nanmean(stack, axis=0)`` and the
+        non-NaN count per cell, reduced on the GPU in a fixed order)."""
+        from hic3defdr_amd.util import apa
+        return apa.apa_mean(stack)
+
     def load_disp_fn(self, cond):
         """Reference ``core.py:220-236`` (after this object's queued write of
         the file has landed)."""

@@ -213,6 +213,20 @@ def cluster_to_loop_id(cluster, chrom, resolution):
                                   (max(y) + 1) * resolution)
 
 
+def cluster_to_slices(cluster, width=21):
+    """Reference ``clusters.py:253-289``: the (row, column) slices of the
+    ``width`` x ``width`` square centred on the cluster's centre of mass
+    (truncated to a bin per axis); ``width`` should be odd.
+
+    >>> cluster_to_slices([(4, 5), (3, 4), (3, 5), (3, 6)], width=5)
+    (slice(1, 6, None), slice(3, 8, None))
+    """
+    half = int((width - 1) / 2)
+    rows, cols = zip(*cluster)
+    r, c = int(np.mean(rows)), int(np.mean(cols))
+    return slice(r - half, r + half + 1), slice(c - half, c + half + 1)
+
+
 def cluster_from_string(cluster_string):
     """Reference ``clusters.py:333-360``."""
     return json.loads(cluster_string.replace('(', '[').replace('{', '[')

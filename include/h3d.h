@@ -29,6 +29,10 @@
  *   h3d_mme_per_pixel      <- util/dispersion.py:83-104 mme_per_pixel
  *                              (Unsmoothed3DeFDR.estimate_disp,
  *                              alternatives.py:119-137)
+ *   h3d_window_gather      <- util/matrices.py:132-160 select_matrix,
+ *                              analysis/core.py:255-291 get_matrix,
+ *                              util/apa.py:6-44 make_apa_stack
+ *   h3d_stack_aggregate    <- np.nanmean over an APA stack (docs/apa.rst)
  *
  * Conventions: 0 on success, a negative H3D_E* code otherwise (the message is
  * in h3d_last_error(), thread-local). Host buffers are C-contiguous and owned
@@ -431,6 +435,54 @@ int h3d_lrt_poisson_dev(h3d_ctx* ctx, const int32_t* d_raw, const double* d_f,
 int h3d_mme_per_pixel(h3d_ctx* ctx, const double* data, const double* f,
                       int64_t n, int R, int C, const int32_t* cond_of_rep,
                       double min_disp, double* disp);
+
+/* ---- dense views (get_matrix / select_matrix / APA) ---------------------- */
+
+/* W dense h x w windows of a sparse matrix in one launch: replaces the
+ * per-window host passes of util/matrices.py:132-160 select_matrix (through
+ * analysis/core.py:255-291 get_matrix) and of util/apa.py:6-44 make_apa_stack
+ * (one scipy slice and toarray per cluster, :36-43).
+ * The matrix is CSR, n_rows x n_cols: indices (nnz) int32 strictly ascending
+ * within a row, data (nnz, ld) float64 row-major, and either indptr
+ * (n_rows + 1) int64 or -- indptr NULL -- row (nnz) int32, the entries sorted
+ * by (row, col) as every outdir table is (the row pointers are then built on
+ * the device, one search per row). cols (K, host memory in both entry points)
+ * lists the data columns taken, each below ld. origins (W, 2) int32 = every
+ * window's (row0, col0); out is (K, W, h, w) float64, or with mean != 0
+ * (W, h, w): the K columns summed in list order, divided by K
+ * (core.py:279-286's np.mean over a condition's replicates).
+ * Cell (r, c) of a window is A[row0 + r, col0 + c] when stored, else `fill`;
+ * with symmetrize != 0 it is A[col0 + c, row0 + r] when that is stored, else
+ * A[row0 + r, col0 + c], else `fill` (select_matrix's second, transposed pass
+ * writes last, matrices.py:156-159). Positions outside the matrix are absent,
+ * so a window may lie partly or wholly outside it. A window whose row0 is
+ * INT32_MIN is all NaN whatever `fill` is (apa.py:38-40). Stored values pass
+ * through bit for bit.
+ * H3D_EARG: h < 1, w < 1, K < 1 (or above 64), a column not below ld,
+ * K * W * h * w >= 2^31, an indptr (host entry) that decreases or leaves
+ * [0, nnz]. W = 0 and nnz = 0 succeed. _dev: every array but cols is a device
+ * pointer; the gather runs on the ctx stream (the inputs must be complete
+ * there) and the call returns once it has finished, like the host entry. */
+int h3d_window_gather(h3d_ctx* ctx, const int64_t* indptr, const int32_t* row,
+                      const int32_t* indices, const double* data, int64_t nnz,
+                      int ld, int n_rows, int n_cols, const int32_t* cols, int K,
+                      const int32_t* origins, int64_t W, int h, int w,
+                      int symmetrize, int mean, double fill, double* out);
+int h3d_window_gather_dev(h3d_ctx* ctx, const int64_t* d_indptr,
+                          const int32_t* d_row, const int32_t* d_indices,
+                          const double* d_data, int64_t nnz, int ld, int n_rows,
+                          int n_cols, const int32_t* cols, int K,
+                          const int32_t* d_origins, int64_t W, int h, int w,
+                          int symmetrize, int mean, double fill, double* d_out);
+
+/* Per-cell aggregate of a stack (W, h, w) of windows (the np.nanmean(stack,
+ * axis=0) that follows util/apa.py:6-44 in an aggregate peak analysis):
+ * count (h, w) int64 = the windows whose cell is not NaN, sum (h, w) = their
+ * sum, in a fixed order (windows in chunks of 128, each chunk summed window
+ * by window, the chunk sums added in chunk order), so a rerun gives the same
+ * bits. Host buffers. W = 0 gives zeros. */
+int h3d_stack_aggregate(h3d_ctx* ctx, const double* stack, int64_t W, int h,
+                        int w, int64_t* count, double* sum);
 
 /* ---- measurement -------------------------------------------------------- */
 
