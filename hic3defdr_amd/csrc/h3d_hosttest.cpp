@@ -40,6 +40,56 @@ H3DT_BINARY(igami, igami)
 H3DT_BINARY(igamci, igamci)
 H3DT_BINARY(chi2_sf, chi2_sf)
 
+H3DT_UNARY(exp_fast, exp_fast)
+H3DT_UNARY(log_fast_checked, log_fast_checked)
+H3DT_UNARY(recip_fast, recip_fast)
+H3DT_BINARY(div_fast, div_fast)
+// exp_fast's gfx950 straight line evaluated here (host build only)
+H3DT_UNARY(exp_fast_straight, exp_fast_straight)
+
+// igam_pq as q2q_core / igam_inv call it: lga = lgam_q2q(a), tail -1 / 0 / 1
+void h3dt_igam_pq(int64_t n, const double* a, const double* x, int tail,
+                  double* P, double* Q, double* fac) {
+  for (int64_t i = 0; i < n; ++i)
+    h3d::igam_pq(a[i], x[i], h3d::lgam_q2q(a[i]), &P[i], &Q[i], &fac[i], tail);
+}
+
+// igam_inv with lga = lgam_q2q(a); guess[i] <= 0: no guess
+void h3dt_igam_inv(int64_t n, const double* a, const double* t, int upper,
+                   const double* guess, double* out) {
+  for (int64_t i = 0; i < n; ++i)
+    out[i] = h3d::igam_inv(a[i], t[i], upper != 0, h3d::lgam_q2q(a[i]),
+                           guess[i] > 0.0 ? guess[i] : -1.0);
+}
+
+// igam_taylor_ok, and igam_step_taylor where it holds (NaN elsewhere)
+void h3dt_igam_step_taylor(int64_t n, const double* a, const double* xe,
+                           const double* h, int32_t* ok, double* dint,
+                           double* ratio) {
+  for (int64_t i = 0; i < n; ++i) {
+    ok[i] = h3d::igam_taylor_ok(a[i], xe[i], h[i]) ? 1 : 0;
+    dint[i] = ratio[i] = NAN;
+    if (ok[i]) h3d::igam_step_taylor(a[i], xe[i], h[i], &dint[i], &ratio[i]);
+  }
+}
+
+// equalize with one alpha per pixel: data (n, r) int32, f (n, r), alpha (n)
+int h3dt_equalize_alpha(int64_t n, int r, const int32_t* x, const double* f,
+                        const double* alpha, double* out) {
+  if (r < 1 || r > M) return -1;
+  int bad = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    double xs[M], fs[M], ps[M];
+    for (int k = 0; k < r; ++k) {
+      xs[k] = x[i * r + k];
+      fs[k] = f[i * r + k];
+    }
+    bad |= h3d::equalize_pixel<M>(xs, fs, r, alpha[i], ps);
+    for (int k = 0; k < r; ++k) out[i * r + k] = ps[k];
+  }
+  return bad;
+}
+
 // log_fast's table bucket of frexp(x)'s mantissa: from its bits (the form in
 // use) and by the FP64 expression it replaced
 void h3dt_log_index(int64_t n, const double* x, int32_t* bits, int32_t* fp) {

@@ -148,8 +148,8 @@ H3D_HD double fit_mu(const TX* x, const double* b, const double* a, int n,
       if (k < n && ((mask >> k) & 1u)) {
         const double mb = mu * b[k];
         const double am = a[k] * mb;
-        // v_rcp_f64 + one Newton step on gfx950 (the IEEE division sequence
-        // was ~12 VALU per replicate and iteration)
+        // v_rcp_f64 + one third-order step on gfx950 (recip_fast; the IEEE
+        // division sequence was ~12 VALU per replicate and iteration)
         const double den = recip_fast(1.0 + am);
         g += (x[k] - mb) * den;
         // g' and g'' in theta: d(mb)/dtheta = mb, d(den)/dtheta = -am den^2
@@ -345,7 +345,14 @@ H3D_HD double q2q_core(double x, double mi, double mo, double alpha,
     // initial guess: carry x through the Wilson-Hilferty cube-root normal
     // approximation of gamma(a_in) into gamma(a_out) -- the approximation
     // errors of the two shapes largely cancel, so Halley usually needs one
-    // step; DiDonato-Morris below shape 1, where Wilson-Hilferty is poor
+    // step; DiDonato-Morris below shape 1, where Wilson-Hilferty is poor, and
+    // beyond 8 sd of its deviate on either side, where the guess is too far
+    // off in the tail for igam_inv's 8 Halley steps (see its LIMIT). Below:
+    // the cube root saturates as x -> 0 (the deviate is bounded by -3
+    // sqrt(a)); wrong from -11.7 sd on, q2q of a count of 1 at a mean of 80
+    // was 4 % off. Above: the two shapes' errors stop cancelling when mu_out
+    // << mu_in; wrong from +9.4 sd on, q2q of 203 at mu_in 25, mu_out 1.26
+    // was 31 % off (tests/test_special_paths.py)
     double guess = -1.0;
     H3D_SEC_BEGIN(t_wh);
     if (a_in >= 1.0 && a_out >= 1.0) {
@@ -362,7 +369,7 @@ H3D_HD double q2q_core(double x, double mi, double mo, double alpha,
       const double zz = (cbrt(div_fast(xs, a_in)) - m_in) * sqrt(9.0 * a_in);
       const double y = m_out + div_fast(zz, sqrt(9.0 * a_out));
 #endif
-      if (y > 0.0) guess = a_out * y * y * y;
+      if (y > 0.0 && fabs(zz) < 8) guess = a_out * y * y * y;
     }
     H3D_SEC_END(5, t_wh);
     H3D_SEC_BEGIN(t_lgo);

@@ -28,7 +28,8 @@ constexpr int kBlock = 256;
 
 enum Op {
   kLgam, kLgamNll, kLogFast, kNdtr, kNdtri, kLog1pmx, kLgam1p,
-  kIgam, kIgamc, kIgami, kIgamci, kChi2Sf, kLogFastFp
+  kIgam, kIgamc, kIgami, kIgamci, kChi2Sf, kLogFastFp,
+  kExpFast, kLogFastChecked, kRecipFast, kDivFast
 };
 
 template <int OP>
@@ -40,6 +41,9 @@ __device__ double unary_op(double x) {
   else if constexpr (OP == kNdtr) return h3d::ndtr(x);
   else if constexpr (OP == kNdtri) return h3d::ndtri(x);
   else if constexpr (OP == kLog1pmx) return h3d::log1pmx(x);
+  else if constexpr (OP == kExpFast) return h3d::exp_fast(x);
+  else if constexpr (OP == kLogFastChecked) return h3d::log_fast_checked(x);
+  else if constexpr (OP == kRecipFast) return h3d::recip_fast(x);
   else return h3d::lgam1p(x);
 }
 
@@ -49,6 +53,7 @@ __device__ double binary_op(double a, double x) {
   else if constexpr (OP == kIgamc) return h3d::igamc(a, x);
   else if constexpr (OP == kIgami) return h3d::igami(a, x);
   else if constexpr (OP == kIgamci) return h3d::igamci(a, x);
+  else if constexpr (OP == kDivFast) return h3d::div_fast(a, x);
   else return h3d::chi2_sf(a, x);
 }
 
@@ -77,6 +82,70 @@ __global__ void k_log_index(int64_t n, const double* __restrict__ x,
     bits[i] = h3d::log_fast_index(m);
     fp[i] = h3d::log_fast_index_fp(m);
   }
+}
+
+__global__ void k_igam_pq(int64_t n, const double* __restrict__ a,
+                          const double* __restrict__ x, int tail,
+                          double* __restrict__ P, double* __restrict__ Q,
+                          double* __restrict__ fac) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double p, q, f;
+    h3d::igam_pq(a[i], x[i], h3d::lgam_q2q(a[i]), &p, &q, &f, tail);
+    P[i] = p;
+    Q[i] = q;
+    fac[i] = f;
+  }
+}
+
+__global__ void k_igam_inv(int64_t n, const double* __restrict__ a,
+                           const double* __restrict__ t, int upper,
+                           const double* __restrict__ guess,
+                           double* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = h3d::igam_inv(a[i], t[i], upper != 0, h3d::lgam_q2q(a[i]),
+                           guess[i] > 0.0 ? guess[i] : -1.0);
+}
+
+__global__ void k_igam_step_taylor(int64_t n, const double* __restrict__ a,
+                                   const double* __restrict__ xe,
+                                   const double* __restrict__ h,
+                                   int32_t* __restrict__ ok,
+                                   double* __restrict__ dint,
+                                   double* __restrict__ ratio) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const bool w = h3d::igam_taylor_ok(a[i], xe[i], h[i]);
+    double d = NAN, r = NAN;
+    if (w) h3d::igam_step_taylor(a[i], xe[i], h[i], &d, &r);
+    ok[i] = w ? 1 : 0;
+    dint[i] = d;
+    ratio[i] = r;
+  }
+}
+
+__global__ void k_equalize_alpha(int64_t n, int r, const int32_t* __restrict__ x,
+                                 const double* __restrict__ f,
+                                 const double* __restrict__ alpha,
+                                 double* __restrict__ pseudo,
+                                 int* __restrict__ status) {
+  int st_all = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double xs[M], fs[M], ps[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const bool on = k < r;
+      xs[k] = on ? (double)x[i * r + k] : 0.0;
+      fs[k] = on ? f[i * r + k] : 1.0;
+    }
+    st_all |= h3d::equalize_pixel<M>(xs, fs, r, alpha[i], ps);
+#pragma unroll
+    for (int k = 0; k < M; ++k)
+      if (k < r) pseudo[i * r + k] = ps[k];
+  }
+  if (st_all) atomicOr(status, st_all);
 }
 
 __global__ void k_fit_mu(int64_t n, int r, const int32_t* __restrict__ x,
@@ -286,6 +355,68 @@ H3DT_BINARY(igamc, kIgamc)
 H3DT_BINARY(igami, kIgami)
 H3DT_BINARY(igamci, kIgamci)
 H3DT_BINARY(chi2_sf, kChi2Sf)
+H3DT_UNARY(exp_fast, kExpFast)
+H3DT_UNARY(log_fast_checked, kLogFastChecked)
+H3DT_UNARY(recip_fast, kRecipFast)
+H3DT_BINARY(div_fast, kDivFast)
+
+void h3dt_igam_pq(int64_t n, const double* a, const double* x, int tail,
+                  double* P, double* Q, double* fac) {
+  Dev<double> da(a, n), dx(x, n), dp(nullptr, n), dq(nullptr, n), df(nullptr, n);
+  hipLaunchKernelGGL(k_igam_pq, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, da.p, dx.p, tail,
+                     dp.p, dq.p, df.p);
+  if (sync_ok()) {
+    dp.to_host(P);
+    dq.to_host(Q);
+    df.to_host(fac);
+  }
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) P[i] = Q[i] = fac[i] = NAN;
+}
+
+void h3dt_igam_inv(int64_t n, const double* a, const double* t, int upper,
+                   const double* guess, double* out) {
+  Dev<double> da(a, n), dt(t, n), dg(guess, n), d(nullptr, n);
+  hipLaunchKernelGGL(k_igam_inv, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, da.p, dt.p, upper,
+                     dg.p, d.p);
+  if (sync_ok()) d.to_host(out);
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) out[i] = NAN;
+}
+
+void h3dt_igam_step_taylor(int64_t n, const double* a, const double* xe,
+                           const double* h, int32_t* ok_out, double* dint,
+                           double* ratio) {
+  Dev<double> da(a, n), dx(xe, n), dh(h, n), dd(nullptr, n), dr(nullptr, n);
+  Dev<int32_t> dok(nullptr, n);
+  hipLaunchKernelGGL(k_igam_step_taylor, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, da.p, dx.p,
+                     dh.p, dok.p, dd.p, dr.p);
+  if (sync_ok()) {
+    dok.to_host(ok_out);
+    dd.to_host(dint);
+    dr.to_host(ratio);
+  }
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) {
+      ok_out[i] = -1;
+      dint[i] = ratio[i] = NAN;
+    }
+}
+
+int h3dt_equalize_alpha(int64_t n, int r, const int32_t* x, const double* f,
+                        const double* alpha, double* out) {
+  if (r < 1 || r > M) return -1;
+  Dev<int32_t> dx(x, n * r);
+  Dev<double> df(f, n * r), da(alpha, n), dp(nullptr, n * r);
+  Dev<int> dst(nullptr, 1);
+  hipLaunchKernelGGL(k_equalize_alpha, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, r, dx.p,
+                     df.p, da.p, dp.p, dst.p);
+  int st = 0;
+  if (!sync_ok()) return -2;
+  dp.to_host(out);
+  dst.to_host(&st);
+  return g_failed ? -2 : st;
+}
 
 void h3dt_log_index(int64_t n, const double* x, int32_t* bits, int32_t* fp) {
   Dev<double> dx(x, n);

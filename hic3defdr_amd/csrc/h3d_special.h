@@ -172,9 +172,11 @@ H3D_HD double lgam(double x) {
   return q;
 }
 
-// 1/y for the NLL lgamma (absolute accuracy): on gfx950 v_rcp_f64 + one
-// Newton step (~1 ulp) instead of the IEEE division sequence; the host
-// build divides.
+// 1/y for the NLL lgamma and the series terms (absolute accuracy): on gfx950
+// v_rcp_f64 + one Newton step instead of the IEEE division sequence; the
+// host build divides. NOT ~1 ulp: v_rcp_f64's estimate is good to ~2^-25, so
+// one step leaves ~2^-49 -- measured on gfx950 up to 9.6 ulp, beyond 2 ulp
+// for 5 % of arguments, at every exponent in [2^-1000, 2^1000].
 H3D_HD double recip_nll(double y) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const double r0 = __builtin_amdgcn_rcp(y);
@@ -184,14 +186,27 @@ H3D_HD double recip_nll(double y) {
 #endif
 }
 
-// 1/y wherever ~1 ulp is enough (Newton iterates of the mean MLE, series
-// terms): recip_nll on gfx950, the division on the host.
-H3D_HD double recip_fast(double y) { return recip_nll(y); }
-// a / b to ~1 ulp by recip_fast (the equalize pass's quantile-map and
-// Halley-step quotients, whose rounding is far below their tests' bars)
+// 1/y to ~1 ulp (Newton iterates of the mean MLE, the q2q quotients): on
+// gfx950 one third-order step on v_rcp_f64's estimate r0, r0 + r0 (e + e^2)
+// with e = 1 - y r0 exact in its fma: the estimate's ~2^-25 cubed is far
+// below an ulp and only the last fma's rounding is left (measured <= 1 ulp;
+// tests/test_special_paths.py asserts 2). One fma more than recip_nll, one
+// fewer than a second Newton step, which measured 1.3 % of the cfg2 step.
+// The division on the host.
+H3D_HD double recip_fast(double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double r0 = __builtin_amdgcn_rcp(y);
+  const double e = fma(-y, r0, 1.0);
+  return fma(fma(e, e, e), r0, r0);
+#else
+  return 1.0 / y;
+#endif
+}
+// a / b by recip_fast (the equalize pass's quantile-map and Halley-step
+// quotients): its ulp and the product's rounding, <= 2 ulp
 H3D_HD double div_fast(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return a * recip_nll(b);
+  return a * recip_fast(b);
 #else
   return a / b;
 #endif
@@ -329,9 +344,19 @@ H3D_HD double stirling_nll(double r2) {
 // 700 (one ballot; the selects would have kept ldexp(p, k) in every lane, so
 // the same bits). Measured (tools/ab_lib.sh, cfg2, round 11): equalize
 // 2.42-2.44 -> 2.38-2.39 ms per step.
-H3D_HD double exp_fast(double x) {
-#if defined(__HIP_DEVICE_COMPILE__)
+// One Horner step of exp_fast's polynomial: hfma in the product; std::fma in
+// exp_fast_straight, the host's evaluation of the same straight line (the
+// host hfma is the unfused p * x + c).
+template <bool kStdFma>
+H3D_HD double exp_fast_step(double p, double x, double c) {
+  return kStdFma ? fma(p, x, c) : hfma(p, x, c);
+}
+
+// exp_fast's reduction x = kd ln2 + r and polynomial: returns e^r, sets *kd_out
+template <bool kStdFma>
+H3D_HD double exp_fast_poly(double x, double* kd_out) {
   const double kd = rint(x * 1.44269504088896338700e+00);
+  *kd_out = kd;
   double r = fma(kd, -6.93147180369123816490e-01, x);
   r = fma(kd, -1.90821492927058770002e-10, r);
 #if H3D_EXP11
@@ -339,47 +364,70 @@ H3D_HD double exp_fast(double x) {
   // ln2 / 2; <= 1.01 ulp with the fused Horner steps against 0.98 for the
   // Taylor form below), two steps and two SGPR constants fewer
   double p = 2.5110037605963777e-08;
-  p = hfma(p, r, 2.763263963904103e-07);
-  p = hfma(p, r, 2.755724091857897e-06);
-  p = hfma(p, r, 2.4801485482328494e-05);
-  p = hfma(p, r, 0.00019841269890047113);
-  p = hfma(p, r, 0.0013888888952314775);
-  p = hfma(p, r, 0.008333333333319601);
-  p = hfma(p, r, 0.0416666666664881);
-  p = hfma(p, r, 0.1666666666666668);
-  p = hfma(p, r, 0.5000000000000019);
-  p = hfma(p, r, 1.0);
-  p = hfma(p, r, 1.0);
+  p = exp_fast_step<kStdFma>(p, r, 2.763263963904103e-07);
+  p = exp_fast_step<kStdFma>(p, r, 2.755724091857897e-06);
+  p = exp_fast_step<kStdFma>(p, r, 2.4801485482328494e-05);
+  p = exp_fast_step<kStdFma>(p, r, 0.00019841269890047113);
+  p = exp_fast_step<kStdFma>(p, r, 0.0013888888952314775);
+  p = exp_fast_step<kStdFma>(p, r, 0.008333333333319601);
+  p = exp_fast_step<kStdFma>(p, r, 0.0416666666664881);
+  p = exp_fast_step<kStdFma>(p, r, 0.1666666666666668);
+  p = exp_fast_step<kStdFma>(p, r, 0.5000000000000019);
+  p = exp_fast_step<kStdFma>(p, r, 1.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0);
 #else
   double p = 1.0 / 6227020800.0;              // 1/13!
-  p = hfma(p, r, 1.0 / 479001600.0);
-  p = hfma(p, r, 1.0 / 39916800.0);
-  p = hfma(p, r, 1.0 / 3628800.0);
-  p = hfma(p, r, 1.0 / 362880.0);
-  p = hfma(p, r, 1.0 / 40320.0);
-  p = hfma(p, r, 1.0 / 5040.0);
-  p = hfma(p, r, 1.0 / 720.0);
-  p = hfma(p, r, 1.0 / 120.0);
-  p = hfma(p, r, 1.0 / 24.0);
-  p = hfma(p, r, 1.0 / 6.0);
-  p = hfma(p, r, 0.5);
-  p = hfma(p, r, 1.0);
-  p = hfma(p, r, 1.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 479001600.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 39916800.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 3628800.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 362880.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 40320.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 5040.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 720.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 120.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 24.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0 / 6.0);
+  p = exp_fast_step<kStdFma>(p, r, 0.5);
+  p = exp_fast_step<kStdFma>(p, r, 1.0);
+  p = exp_fast_step<kStdFma>(p, r, 1.0);
 #endif
-#if H3D_EXP_UNIFORM
-  // a wave whose active lanes are all finite and inside (-700, 700): the
-  // clamp and the three selects below would pick ldexp(p, kd) in every lane
-  // (one wave-uniform test instead of them)
-  if (__builtin_amdgcn_ballot_w64(!(fabs(x) < 700.0)) == 0) return ldexp(p, (int)kd);
-#endif
+  return p;
+}
+
+// exp_fast's scaling p 2^kd for any x: the clamp of k and the overflow /
+// underflow / NaN selects
+H3D_HD double exp_fast_scale(double x, double p, double kd) {
   const int k = (int)fmax(fmin(kd, 1100.0), -1100.0);
   double v = ldexp(p, k);
   v = (x > 7.09782712893383996843e2) ? INFINITY : v;
   v = (x < -7.45133219101941108420e2) ? 0.0 : v;
   return (x != x) ? x : v;
+}
+
+H3D_HD double exp_fast(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double kd;
+  const double p = exp_fast_poly<false>(x, &kd);
+#if H3D_EXP_UNIFORM
+  // a wave whose active lanes are all finite and inside (-700, 700): the
+  // clamp and the three selects of exp_fast_scale would pick ldexp(p, kd) in
+  // every lane (one wave-uniform test instead of them)
+  if (__builtin_amdgcn_ballot_w64(!(fabs(x) < 700.0)) == 0) return ldexp(p, (int)kd);
+#endif
+  return exp_fast_scale(x, p, kd);
 #else
   return exp(x);
 #endif
+}
+
+// exp_fast's gfx950 branch without the wave-uniform shortcut, every Horner
+// step a std::fma: the same correctly rounded operations in any build, so
+// the host build checks the polynomial and the selects, and the gfx950
+// exp_fast must return these bits (tests only: test_special_paths.py)
+H3D_HD double exp_fast_straight(double x) {
+  double kd;
+  const double p = exp_fast_poly<true>(x, &kd);
+  return exp_fast_scale(x, p, kd);
 }
 
 // degree-5 rising factorial x (x+1) (x+2) (x+3) (x+4)
@@ -751,8 +799,11 @@ H3D_HD double igamc_cf(double a, double x) {
 // other is 1 - it.
 // tail = 1 / 0: the caller needs Q / P accurately. Then the method that
 // converges fastest for that tail is used -- the power series (Q = 1 - P)
-// for Q within 3 sqrt(a) of the mean at shapes a < 8, else the continued
-// fraction for Q whenever x > 1; the power series for P up to x < 1.5 a + 5
+// for Q within 3 sqrt(a) of the mean at shapes a < 8 and below a - sqrt(a) / 2
+// (there Q > 1/2, and the fraction converges ever slower as x falls below a:
+// capped at kMaxIter steps it left Q(2e4, a - 1.28 sqrt(a)) 5e-9 off), else
+// the continued fraction for Q whenever x > 1; the power series for P up to
+// x < 1.5 a + 5
 // -- instead of cephes' x-vs-a switch, so lanes of a wave that want the same
 // tail mostly take the same branch. tail = -1: the cephes rule.
 H3D_HD void igam_pq(double a, double x, double lga, double* P, double* Q,
@@ -782,7 +833,9 @@ H3D_HD void igam_pq(double a, double x, double lga, double* P, double* Q,
   // the larger shapes (census, tools/q2q_stats.py: the equalize pass' loop
   // cost per wave -26 .. -34 %, modelled lane utilisation 0.77 -> 0.81)
   const double xa = x - a;
-  const bool use_cf = (tail == 1)   ? (x > 1.0 && !(a < 8.0 && xa * xa < 9.0 * a))
+  const double xa2 = xa * xa;
+  const bool use_cf = (tail == 1)   ? (x > 1.0 && !(a < 8.0 && xa2 < 9.0 * a) &&
+                                       !(xa < 0.0 && xa2 > 0.25 * a))
                      : (tail == 0) ? (x > 1.0 && x > a && !(x < 1.5 * a + 5.0))
                                    : (x > 1.0 && x > a);
   if (use_cf) {  // continued fraction for the upper tail
@@ -1048,10 +1101,14 @@ H3D_HD double find_inverse_gamma(double a, double p, double q, double lga) {
 // and exp(g) = sum e_k s^k by the power-series exponential recurrence
 // e_k = (1/k) sum_j j g_j e_(k-j) on g's Taylor coefficients
 // g_j = (a-1) (-1)^(j+1) / (j xe^j) (- 1 for j = 1). K = 12 terms, fixed
-// length (no lane divergence). Used inside the window igam_taylor_ok, where
-// the dropped terms are below (|g_1 h|)^13 / 13! and |a-1| (h/xe)^13 / 13,
-// i.e. < 2e-15 x/h of the increment -- the root it leads to moves < 1e-16
-// relative.
+// length (no lane divergence). Used inside the window igam_taylor_ok. The
+// dropped terms: (|g_1 h|)^13 / 13! and |a-1| (h/xe)^13 / 13, < 2e-15 -- and
+// the powers of g's second-order term, (|a-1| (h/xe)^2 / 2)^7 / 7! <= 1e-10 at
+// the window's limit |a-1| (h/xe)^2 = 1/4 (measured there: 7e-10 of the
+// ratio, 5e-11 of the increment; tests/test_special_paths.py). That limit
+// has |h/xe| <= 1 / (2 sqrt|a-1|), so the root the step leads to moves by <
+// 5e-11 |h/xe|, ~1e-12 relative at most, and by < 1e-16 for the confirming
+// steps (|h/xe| ~ 1e-4) that take this path in the equalize pass.
 constexpr int kTaylorK = 12;
 
 // (one ~1-ulp reciprocal of xe for both quotients: a window test, and a
@@ -1108,6 +1165,13 @@ H3D_HD void igam_step_taylor(double a, double xe, double h, double* dint,
 // costs ~40 flops instead of a series / continued fraction. A good guess
 // (~1e-4 relative) thus takes ONE incomplete-gamma evaluation: the confirming
 // Halley step runs on the continuation.
+//
+// LIMIT: Halley on the tail itself converges only linearly from a guess
+// whose tail is orders of magnitude off, and the loop has 8 steps: a guess 5 %
+// off is recovered for t >= ~1e-15 only, and comes back nearly unchanged at t
+// = 1e-200 (tests/test_special_paths.py measures both). There is no restart:
+// the caller vouches for its guess. q2q_core's Wilson-Hilferty guess is that
+// far off only below -11 sd of its deviate and is gated at -8 sd there.
 H3D_HD double igam_inv(double a, double t, bool upper, double lga,
                        double guess = -1.0, const LogTab* tab = kLogTab) {
   H3D_STAT(inv, 1);
