@@ -37,6 +37,7 @@ EXPORTS = [
     'h3d_scale_disp_dev', 'h3d_npz_backend', 'h3d_npz_csr_read_slack',
     'h3d_pixel_f_dev', 'h3d_read_text_column', 'h3d_set_qcml_tol',
     'h3d_window_gather', 'h3d_window_gather_dev', 'h3d_stack_aggregate',
+    'h3d_filter_sparse_rows', 'h3d_kr_balance',
 ]
 
 
@@ -62,6 +63,7 @@ H3D_EINPUT = -5
 
 
 _P = ctypes.c_void_p
+_INT_MAX = 2 ** 31 - 1
 _I64 = ctypes.c_int64
 _I = ctypes.c_int
 _D = ctypes.c_double
@@ -170,6 +172,10 @@ def load_library(path=None):
                                            _I, _P, _I, _P, _I64, _I, _I, _I,
                                            _I, _D, _P]),
             'h3d_stack_aggregate': (_I, [_P, _P, _I64, _I, _I, _P, _P]),
+            'h3d_filter_sparse_rows': (_I, [_P, _P, _P, _P, _I, _I64, _I, _I,
+                                            _P, _P, _P, _P, _P]),
+            'h3d_kr_balance': (_I, [_P, _P, _P, _P, _I, _I64, _I, _I, _D, _D,
+                                    _D, _I, _P, _P, _P, _P, _P, _P, _I]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -765,6 +771,75 @@ class Context(object):
                                             _ptr(count), _ptr(total)),
                'h3d_stack_aggregate')
         return count, total
+
+    # -- sparse-bin filter and KR balancing ----------------------------------
+    @staticmethod
+    def _csr_args(indptr, indices, data, n):
+        indptr = _c(indptr, np.int64)
+        indices = _c(indices, np.int32)
+        data = _c(data, np.float64)
+        if len(indptr) != n + 1 or len(indices) != len(data):
+            raise ValueError('indptr must have n + 1 entries, indices and '
+                             'data one per stored entry')
+        return indptr, indices, data
+
+    def filter_sparse_rows(self, indptr, indices, data, n, min_nnz=25, k=300):
+        """filter_sparse_rows_count on a square CSR matrix of ``n`` bins
+        (h3d_filter_sparse_rows): (indptr, indices, data) of the kept entries
+        and the number of wiped bins."""
+        indptr, indices, data = self._csr_args(indptr, indices, data, n)
+        nnz = len(data)
+        out_indptr = np.empty(n + 1, dtype=np.int64)
+        out_indices = np.empty(nnz, dtype=np.int32)
+        out_data = np.empty(nnz, dtype=np.float64)
+        kept, wiped = _I64(0), _I64(0)
+        _check(self.lib.h3d_filter_sparse_rows(
+            self.handle, _ptr(indptr), _ptr(indices), _ptr(data), n, nnz,
+            min(int(min_nnz), _INT_MAX), min(int(k), _INT_MAX),
+            _ptr(out_indptr), _ptr(out_indices),
+            _ptr(out_data), ctypes.byref(kept), ctypes.byref(wiped)),
+            'h3d_filter_sparse_rows')
+        return (out_indptr, out_indices[:kept.value].copy(),
+                out_data[:kept.value].copy(), wiped.value)
+
+    KR_STATS = ('outer', 'inner', 'low_clamps', 'high_clamps', 'wiped',
+                'rows')
+
+    def kr_balance(self, indptr, indices, data, n, min_nnz=0, k=0, tol=1e-6,
+                   lo=0.1, hi=3, max_iter=3000, x0=None, balanced=False):
+        """The sparse-bin filter (skipped at ``min_nnz`` or ``k`` 0) and the
+        Knight-Ruiz balancing of an upper-triangular canonical CSR matrix in
+        one device pass (h3d_kr_balance). ``x0``: (n,) start vector by bin,
+        or None; ``max_iter`` None: no cap. Returns a dict: ``bias`` (n,),
+        ``balanced`` (nnz,) the balanced value of every input entry (None
+        unless asked for), ``stats`` (KR_STATS -> int), ``inner`` / ``norms``
+        the inner steps and residual norm of every outer step."""
+        indptr, indices, data = self._csr_args(indptr, indices, data, n)
+        nnz = len(data)
+        if x0 is not None:
+            x0 = _c(x0, np.float64)
+            if x0.shape != (n,):
+                raise ValueError('x0 must have one value per bin')
+        # (the library stops after 10,000 inner steps, so outer steps too)
+        cap = 10002 if max_iter is None else min(max(int(max_iter), 0) + 2,
+                                                  10002)
+        bias = np.empty(n, dtype=np.float64)
+        bal = np.empty(nnz, dtype=np.float64) if balanced else None
+        stats = np.zeros(6, dtype=np.int64)
+        inner = np.zeros(cap, dtype=np.int32)
+        norms = np.zeros(cap, dtype=np.float64)
+        _check(self.lib.h3d_kr_balance(
+            self.handle, _ptr(indptr), _ptr(indices), _ptr(data), n, nnz,
+            min(int(min_nnz), _INT_MAX), min(int(k), _INT_MAX), float(tol),
+            float(lo), float(hi),
+            -1 if max_iter is None else min(int(max_iter), _INT_MAX),
+            _ptr(x0), _ptr(bias),
+            _ptr(bal), _ptr(stats), _ptr(inner), _ptr(norms), cap),
+            'h3d_kr_balance')
+        m = min(int(stats[0]), cap)
+        return dict(bias=bias, balanced=bal,
+                    stats=dict(zip(self.KR_STATS, (int(v) for v in stats))),
+                    inner=inner[:m].copy(), norms=norms[:m].copy())
 
     # -- measurement ---------------------------------------------------------
     def profile(self, on=True, level=2):

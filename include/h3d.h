@@ -33,6 +33,9 @@
  *                              analysis/core.py:255-291 get_matrix,
  *                              util/apa.py:6-44 make_apa_stack
  *   h3d_stack_aggregate    <- np.nanmean over an APA stack (docs/apa.rst)
+ *   h3d_filter_sparse_rows <- util/filtering.py:8-33 filter_sparse_rows_count
+ *   h3d_kr_balance         <- util/balancing.py:5-208 kr_balance (behind the
+ *                              filter: README.md:602-614)
  *
  * Conventions: 0 on success, a negative H3D_E* code otherwise (the message is
  * in h3d_last_error(), thread-local). Host buffers are C-contiguous and owned
@@ -484,6 +487,57 @@ int h3d_window_gather_dev(h3d_ctx* ctx, const int64_t* d_indptr,
 int h3d_stack_aggregate(h3d_ctx* ctx, const double* stack, int64_t W, int h,
                         int w, int64_t* count, double* sum);
 
+/* ---- sparse-bin filter and KR balancing (simulation workflow) ------------- */
+
+/* util/filtering.py:8-33 filter_sparse_rows_count on a square CSR matrix
+ * (indptr (n + 1) int64, indices (nnz) int32, data (nnz) float64; host
+ * buffers, duplicates summed): down[i] / up[j] count the entries with
+ * 1 <= col - row <= min(n, k) and data > 0 per row / per column; a bin with
+ * up < min_nnz and down < min_nnz is wiped, and an entry whose row or column
+ * is wiped leaves, as does a stored 0 (the reference's sparse products drop
+ * it). The kept entries come back in their order: out_indptr (n + 1),
+ * out_indices / out_data (capacity nnz), *nnz_out their count; *n_wiped
+ * (nullable) the wiped bins. min_nnz == 0 or k == 0: nothing leaves
+ * (filtering.py:16-17). H3D_EARG: indptr not ascending from 0 to nnz,
+ * nnz >= 2^30; H3D_EINPUT: a column outside [0, n). */
+int h3d_filter_sparse_rows(h3d_ctx* ctx, const int64_t* indptr,
+                           const int32_t* indices, const double* data, int n,
+                           int64_t nnz, int min_nnz, int k, int64_t* out_indptr,
+                           int32_t* out_indices, double* out_data,
+                           int64_t* nnz_out, int64_t* n_wiped);
+
+/* The filter above (skipped when min_nnz == 0 or k == 0) followed by
+ * util/balancing.py:5-208 kr_balance in one device pass: the README's loop
+ * over the simulated replicates (README.md:602-614). The matrix is upper
+ * triangular, canonical CSR (columns ascending from the row's own, no
+ * duplicates; host buffers as above); an entry of value 0 is no entry. The
+ * device builds the symmetric matrix of the kept entries (rows in ascending
+ * column order, the diagonal once) and runs the Knight-Ruiz iteration on the
+ * rows that have entries: Newton steps on x (A x) = 1 until
+ * |1 - x (A x)|^2 <= tol^2 or more than max_iter steps (max_iter < 0: no
+ * cap), each a conjugate-gradient solve clamped to the box [lo, hi]
+ * (kr_balance's delta / ddelta); x0 (nullable, n values, those of rows
+ * without entries ignored) is the start vector, default ones. Then
+ * scale = x sqrt(sum(A) / sum(diag(x) A diag(x))), bias_out (n) = 1 / scale,
+ * 0 for the rows without entries -- all NaN when no row has entries, as the
+ * reference's 0 * sqrt(0 / 0). balanced_out (nullable, nnz): a_ij s_i s_j of
+ * every input entry (0 for the entries that left).
+ * stats (6) = {outer steps, inner steps in total, low-clamp hits, high-clamp
+ * hits, bins wiped by the filter, rows in the iteration}; hist_inner /
+ * hist_norm (nullable, capacity hist_cap): inner steps and |1 - x (A x)|
+ * of the first hist_cap outer steps (the reference's "it in. it res" table).
+ * Every sum has a fixed order: a rerun gives the same bits.
+ * H3D_ENOCONV: more than 10,000 inner steps in total (the reference's inner
+ * loop has no cap), or a clamp without a candidate step (the reference
+ * raises); H3D_EINPUT: a column outside [row, n); H3D_EARG: negative or NaN
+ * tol, indptr not ascending from 0 to nnz, nnz >= 2^30. */
+int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
+                   const double* data, int n, int64_t nnz, int min_nnz, int k,
+                   double tol, double lo, double hi, int max_iter,
+                   const double* x0, double* bias_out, double* balanced_out,
+                   int64_t* stats, int32_t* hist_inner, double* hist_norm,
+                   int hist_cap);
+
 /* ---- measurement -------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on the ctx stream; on = 0 off, 1 the roofline
@@ -492,7 +546,9 @@ int h3d_stack_aggregate(h3d_ctx* ctx, const double* stack, int64_t W, int h,
  * equalize pass), "disp_nll", "disp_reduce", "disp_update", "disp_prep",
  * "lrt"}. units: algorithmic HBM bytes for "disp_work" / "disp_nll"
  * (counted on the device since the last reset), pixels for "lrt" /
- * "disp_prep". name "gang_aborts": *launches = gang Brent waits of the ctx
+ * "disp_prep"; h3d_kr_balance's stages are "kr_filter", "kr_symmetrise",
+ * "kr_iter" (the Newton loop, its record reads included) and "kr_rescale".
+ * name "gang_aborts": *launches = gang Brent waits of the ctx
  * that timed out (the searches then finished under k_brent). */
 int h3d_profile_enable(h3d_ctx* ctx, int on);
 int h3d_profile_read(h3d_ctx* ctx, const char* name, double* total_ms,
