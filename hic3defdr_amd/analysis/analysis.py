@@ -117,7 +117,7 @@ class AnalyzingHiC3DeFDR(object):
 
     def _barrier(self, sh):
         """The end of a sharded stage: this rank's queued outdir writes land
-        first (core.py's write-behind), then the ranks meet -- so after the
+        first (outdir.py's write-behind), then the ranks meet -- so after the
         barrier every rank's files of the stage are on disk for any rank
         (threshold / classify / collect read every chromosome)."""
         if sh.dist is not None:

@@ -5,7 +5,7 @@ The reference's stages hand their data over through the outdir only
 ``analysis.py:128-133``; estimate_disp reads them back and rebuilds
 ``f = bias[row] * bias[col] * size_factors``, ``:169-183``; lrt reads them
 and ``disp`` again and rebuilds ``f``, ``:261-275``). The outdir contract is
-kept -- every file is written (core.py's write-behind queue) -- but within
+kept -- every file is written (outdir.py's write-behind queue) -- but within
 one object the data also stays in HBM:
 
 * prepare_data leaves each chromosome's union (row, col, raw as int32, size
@@ -24,30 +24,22 @@ one object the data also stays in HBM:
   it would read are the ones lrt wrote.
 
 A resident entry is used only while the outdir files it mirrors are the
-ones it was made from (core.CoreHiC3DeFDR.is_current, or the file stamps
-taken when it was loaded from disk) and the bias files are unchanged, so
-edits of the outdir are always seen. Device buffers are torch tensors (the
-allocator); every computation on them is libh3d's.
+ones it was made from (the tokens of the object's outdir.OutdirStore: its
+own write of the file, or the file's stamp when it was loaded from disk)
+and the bias files are unchanged, so edits of the outdir are always seen.
+Device buffers are torch tensors (the allocator); every computation on them
+is libh3d's.
 """
-import os
-
 import numpy as np
 
 from hic3defdr_amd import _native
 from hic3defdr_amd.analysis.d2h import to_host_async
-
-
-def _stamp(fname):
-    try:
-        st = os.stat(fname)
-    except OSError:
-        return None
-    return (st.st_ino, st.st_size, st.st_mtime_ns, st.st_ctime_ns)
+from hic3defdr_amd.analysis.outdir import disk_token
 
 
 def bias_stamps(bias_patterns, chrom):
-    """{bias file: ('disk', stamp)} of one chromosome's bias files."""
-    return {f: ('disk', _stamp(f)) for f in
+    """{bias file: its disk token} of one chromosome's bias files."""
+    return {f: disk_token(f) for f in
             (p.replace('<chrom>', chrom) for p in bias_patterns)}
 
 
@@ -60,7 +52,7 @@ class ChromDev(object):
         self.sf, self.sf_per_rep = sf, sf_per_rep
         self.disp_idx, self.n_disp = disp_idx, n_disp
         self.bias = bias      # host (n_bins, R), bias_thresh-filtered
-        self.files = files    # fname -> ('ours', generation) / ('disk', stamp)
+        self.files = files    # fname -> its token (outdir.OutdirStore.token)
         self.n = int(row.shape[0])
 
 
@@ -81,21 +73,12 @@ class Resident(object):
 
     # -- validity --------------------------------------------------------
     def _current(self, files):
-        for fname, (kind, tok) in files.items():
-            if kind == 'ours':
-                if self.h.write_generation(fname) != tok or \
-                        not self.h.is_current(fname):
-                    return False
-            elif _stamp(fname) != tok:
-                return False
-        return True
+        store = self.h._store
+        return all(store.token_valid(f, t) for f, t in files.items())
 
-    def _token(self, fname):
-        """('ours', generation) for an outdir file this object wrote and
-        that is still that write, else ('disk', file stamp)."""
-        if self.h.is_current(fname):
-            return ('ours', self.h.write_generation(fname))
-        return ('disk', _stamp(fname))
+    def _tokens(self, fnames):
+        store = self.h._store
+        return {f: store.token(f) for f in fnames}
 
     def _bias_stamps(self, chrom):
         return bias_stamps(self.h.bias_patterns, chrom)
@@ -187,8 +170,7 @@ class Resident(object):
         if t_di is None:
             t_di = torch.from_numpy(np.ascontiguousarray(
                 disp_idx, dtype=np.uint8)).to(self.dev)
-        files = {self.h._npy(s, chrom): ('ours', self.h.write_generation(
-            self.h._npy(s, chrom))) for s in self.STAGES}
+        files = self._tokens(self.h._npy(s, chrom) for s in self.STAGES)
         files.update(bias_stamps if bias_stamps is not None
                      else self._bias_stamps(chrom))
         self.chroms[chrom] = ChromDev(
@@ -212,12 +194,9 @@ class Resident(object):
         prepared: read from the outdir files and uploaded once."""
         torch = self.torch
         h = self.h
-        files = {}
-        arrs = {}
-        for s in self.STAGES:
-            fname = h._npy(s, chrom)
-            files[fname] = self._token(fname)
-            arrs[s] = h.load_data(s, chrom)
+        # tokens before the reads: a file replaced in between shows as changed
+        files = self._tokens(h._npy(s, chrom) for s in self.STAGES)
+        arrs = {s: h.load_data(s, chrom) for s in self.STAGES}
         files.update(self._bias_stamps(chrom))
         raw = np.asarray(arrs['raw'])
         if raw.size and (raw.min() < 0 or raw.max() > np.iinfo(np.int32).max):
@@ -316,9 +295,8 @@ class Resident(object):
         """estimate_disp's resident result for lrt: its pixels and device
         tables, valid while its disp files and its chromosomes' stage files
         are current; ``lrt_bufs`` (lrt_buffers) for the first lrt on it."""
-        files = {}
+        files = self._tokens(self.h._npy('disp', c) for c in chroms)
         for c in chroms:
-            files[self.h._npy('disp', c)] = self._token(self.h._npy('disp', c))
             files.update(self.chroms[c].files)
         self.session = {'chroms': tuple(chroms), 'raw': t_raw, 'f': t_f,
                         'dist': t_dist, 'offsets': offsets, 'tables': t_tab,
@@ -327,8 +305,7 @@ class Resident(object):
     def keep_pvalues(self, chroms, t_p, offsets):
         """lrt's device p-values of ``chroms`` (its pvalues files just
         queued), for bh while those files are current."""
-        files = {self.h._npy('pvalues', c): self._token(
-            self.h._npy('pvalues', c)) for c in chroms}
+        files = self._tokens(self.h._npy('pvalues', c) for c in chroms)
         self.pvals = {'chroms': tuple(chroms), 'p': t_p, 'offsets': offsets,
                       'files': files}
 

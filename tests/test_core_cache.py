@@ -72,8 +72,8 @@ def test_same_size_rewrite_in_place_with_mtime_restored():
 
 
 def test_cache_is_bounded_lru(monkeypatch):
-    from hic3defdr_amd.analysis.core import CoreHiC3DeFDR
-    monkeypatch.setattr(CoreHiC3DeFDR, '_CACHE_BYTES', 3 * 800)
+    from hic3defdr_amd.analysis.outdir import OutdirStore
+    monkeypatch.setattr(OutdirStore, 'CACHE_BYTES', 3 * 800)
     h = _h()
     for i in range(10):                  # 10 chromosomes' worth of stages
         h.save_data(np.full(100, float(i)), 'pvalues', 'chr%d' % i)
@@ -83,7 +83,7 @@ def test_cache_is_bounded_lru(monkeypatch):
     for i in range(10):                  # evicted ones come from disk
         np.testing.assert_array_equal(h.load_data('pvalues', 'chr%d' % i),
                                       np.full(100, float(i)))
-    monkeypatch.setattr(CoreHiC3DeFDR, '_CACHE_BYTES', 0)
+    monkeypatch.setattr(OutdirStore, 'CACHE_BYTES', 0)
     h2 = _h()
     h2.save_data(np.zeros(10), 'pvalues', 'chr1')
     h2.flush()
@@ -108,14 +108,14 @@ def test_write_behind_queue(monkeypatch):
     waits for it, writes of one file land in order, and the queued array
     cannot be changed under the writer."""
     import threading
-    from hic3defdr_amd.analysis import core
+    from hic3defdr_amd.analysis import outdir
     gate = threading.Event()
-    real = core._write_npy
+    real = outdir._write_npy
 
     def slow(fname, data, ready=None):
         gate.wait(10)
         return real(fname, data, ready)
-    monkeypatch.setattr(core, '_write_npy', slow)
+    monkeypatch.setattr(outdir, '_write_npy', slow)
     h = _h()
     fname = os.path.join(h.outdir, 'pvalues_chr1.npy')
     h.save_data(np.zeros(4), 'pvalues', 'chr1')
@@ -136,20 +136,20 @@ def test_write_behind_queue(monkeypatch):
 def test_pending_writes_are_bounded_without_flush(monkeypatch):
     """Saving many chromosomes' stages without flush(): landed writes move
     into the size-limited cache on the next save, and the queued bytes stay
-    under _PENDING_BYTES even while the writer is slow (the save waits)."""
+    under PENDING_BYTES even while the writer is slow (the save waits)."""
     import threading
-    from hic3defdr_amd.analysis import core
-    from hic3defdr_amd.analysis.core import CoreHiC3DeFDR
-    monkeypatch.setattr(CoreHiC3DeFDR, '_CACHE_BYTES', 4 * 800)
-    monkeypatch.setattr(CoreHiC3DeFDR, '_PENDING_BYTES', 3 * 800)
-    real = core._write_npy
+    from hic3defdr_amd.analysis import outdir
+    from hic3defdr_amd.analysis.outdir import OutdirStore
+    monkeypatch.setattr(OutdirStore, 'CACHE_BYTES', 4 * 800)
+    monkeypatch.setattr(OutdirStore, 'PENDING_BYTES', 3 * 800)
+    real = outdir._write_npy
     started = threading.Semaphore(0)
 
     def slow(fname, data, ready=None):
         started.release()
         time.sleep(0.002)
         return real(fname, data, ready)
-    monkeypatch.setattr(core, '_write_npy', slow)
+    monkeypatch.setattr(outdir, '_write_npy', slow)
     h = _h()
     peak = 0
     for i in range(40):
@@ -169,11 +169,12 @@ def test_landed_writes_leave_the_queue_on_the_next_save():
     h = _h()
     h.save_data(np.zeros(1000), 'pvalues', 'chr1')
     deadline = time.time() + 10
-    while h._pending()[os.path.join(h.outdir, 'pvalues_chr1.npy')][0].done() \
+    pending = h._store.pending
+    while pending[os.path.join(h.outdir, 'pvalues_chr1.npy')].future.done() \
             is False and time.time() < deadline:
         time.sleep(0.001)
     h.save_data(np.zeros(10), 'llr', 'chr1')
-    assert os.path.join(h.outdir, 'pvalues_chr1.npy') not in h._pending()
+    assert os.path.join(h.outdir, 'pvalues_chr1.npy') not in pending
     assert h.cache_nbytes() >= 8000
     h.flush()
 
@@ -204,13 +205,13 @@ def test_ready_callable_runs_before_write_and_read():
 
 def test_evicted_large_arrays_are_released_off_the_main_thread(monkeypatch):
     """The cache's evictions hand large arrays to the background reaper
-    (core._Reaper): each is released once the reaper has run, and the
+    (outdir._Reaper): each is released once the reaper has run, and the
     files and later reads are unaffected."""
     import gc
     import weakref
-    from hic3defdr_amd.analysis import core
-    monkeypatch.setattr(HiC3DeFDR, '_CACHE_BYTES', 40 << 20)
-    monkeypatch.setattr(core._Reaper, '_MIN_BYTES', 1 << 20)
+    from hic3defdr_amd.analysis import outdir
+    monkeypatch.setattr(outdir.OutdirStore, 'CACHE_BYTES', 40 << 20)
+    monkeypatch.setattr(outdir._Reaper, '_MIN_BYTES', 1 << 20)
     h = _h()
     refs = []
     for k in range(4):
@@ -219,7 +220,7 @@ def test_evicted_large_arrays_are_released_off_the_main_thread(monkeypatch):
         h._save_npy(h._npy('scaled', 'chr%d' % k), a, owned=True)
         del a
         h.flush()
-        h._settle_landed()
+        h._store.settle_landed()
     # two of the four fit the 40 MB cache: the older ones were evicted
     deadline = time.time() + 10
     while time.time() < deadline and (refs[0]() is not None or

@@ -6,6 +6,7 @@ and h3d_scale_disp_dev against the reference's numpy expressions
 import os
 import shutil
 import tempfile
+import time
 
 import numpy as np
 import pandas as pd
@@ -151,6 +152,57 @@ def test_bh_uses_device_pvalues_only_while_their_files_are_current():
         h.bh()
         h.flush()
         check()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+@pytest.mark.parametrize('how', ['save_data', 'np_save_after_flush'])
+def test_lrt_uses_the_session_only_while_its_disp_files_are_current(how):
+    """lrt runs on estimate_disp's session right after it, and from the
+    outdir files once a disp file was rewritten -- through the object, or
+    behind it after flush(): its outputs then equal, bit for bit, those of a
+    fresh object loaded from the outdir."""
+    from hic3defdr_amd import HiC3DeFDR
+    g, kw = e2e_inputs('small2')
+    design = pd.DataFrame(kw['design'], index=kw['reps'], columns=kw['conds'])
+    tmp = tempfile.mkdtemp(prefix='h3d_lrt_')
+    names = ('pvalues', 'llr', 'mu_hat_null', 'mu_hat_alt')
+    try:
+        h = HiC3DeFDR(raw_npz_patterns=kw['raw_npz_patterns'],
+                      bias_patterns=kw['bias_patterns'], chroms=kw['chroms'],
+                      design=design, outdir=tmp,
+                      dist_thresh_max=kw['dist_thresh_max'],
+                      loop_patterns=kw['loop_patterns'], res=10000)
+        h.prepare_data(verbose=False)
+        h.estimate_disp()
+        res = h.__dict__['_dev_resident']
+        assert res.lrt_session(h.chroms) is not None
+        h.lrt(verbose=False)
+        h.flush()
+        llr0 = {c: h.load_data('llr', c) for c in h.chroms}
+        # rewrite one chromosome's disp: lrt must read the files now
+        c0 = h.chroms[0]
+        disp2 = 2 * h.load_data('disp', c0)
+        if how == 'save_data':
+            h.save_data(disp2, 'disp', c0)
+        else:
+            time.sleep(0.02)             # past the clock tick of the mtime
+            np.save(h._npy('disp', c0), disp2)
+        assert res.lrt_session(h.chroms) is None
+
+        def run(obj):
+            obj.lrt(verbose=False)
+            obj.flush()
+            return {(s, c): obj.load_data(s, c) for s in names
+                    for c in obj.chroms}
+        a = run(h)
+        b = run(HiC3DeFDR.load(tmp))
+        for key in a:
+            assert a[key].dtype == b[key].dtype, key
+            np.testing.assert_array_equal(a[key].view(np.int64),
+                                          b[key].view(np.int64),
+                                          err_msg='%s %s' % key)
+        assert np.any(a['llr', c0] != llr0[c0])
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
