@@ -221,25 +221,31 @@ __global__ __launch_bounds__(kBlock, 2) void k_lrt8(
     // llr as lrt_pixel forms it: per replicate x log(mu0 / mu1) - (r + x)
     // log((r + m0) / (r + m1)) (the logpmf rows' difference term by term),
     // one log per replicate and one per condition
+    // (the logs through log_quot, as lrt_pixel)
     double lq[CM];
+    bool near[CM];
 #pragma unroll
-    for (int c = 0; c < CM; ++c)
-      lq[c] = (c < C) ? log_fast_checked(div_fast(m0, m1[c]), s_tab) : 0.0;
+    for (int c = 0; c < CM; ++c) {
+      near[c] = c < C && m0 >= 0.5 * m1[c] && m0 <= 2.0 * m1[c];
+      lq[c] = (c < C) ? log_quot(m0, m1[c], m0 - m1[c], near[c], s_tab) : 0.0;
+    }
     double part = 0.0;
 #pragma unroll
     for (int s = 0; s < J; ++s) {
       if (lane + kGroup * s >= R) continue;
       double m1k = 0.0, l = 0.0;
+      bool nr = false;
 #pragma unroll
       for (int c = 0; c < CM; ++c)
         if (c == cnd[s]) {
           m1k = m1[c];
           l = lq[c];
+          nr = near[c];
         }
       const double xk = (double)x[s];
       const double r = 1.0 / a[s];
-      const double lr =
-          log_fast_checked(div_fast(r + m0 * fv[s], r + m1k * fv[s]), s_tab);
+      const double lr = log_quot(r + m0 * fv[s], r + m1k * fv[s], (m0 - m1k) * fv[s],
+                                 nr, s_tab);
       part += xk * l - (r + xk) * lr;
     }
     const double lv = gsum8(part);

@@ -421,6 +421,28 @@ H3D_HD double logpmf(double k, double m, double phi) {
          k * log(m) - k * log(r + m);
 }
 
+// log(num / den) where num = den + d, for the llr's quotients mu0 / mu1 and
+// (r + mu0 f) / (r + mu1 f). The rounded quotient q carries half an ulp of
+// relative error, i.e. ~1e-16 ABSOLUTE in log q whatever its size, and the llr
+// multiplies it by the count: at counts of 1e8 and mu0 ~ mu1 that is ~1e-8 per
+// replicate on an llr of ~1e-3, which moved p of a two-condition design past
+// the 1e-6 bar at x2 ~ 2e-3 (the exact fixture of tests/lrt_mp_cases.py holds
+// it). `near` (mu1 / 2 <= mu0 <= 2 mu1, so d = mu0 -
+// mu1 is exact and both quotients lie in [1/2, 2]): log1p(e) at e = d / den,
+// whose rounding is relative to e, as log(u) + c / u with u = 1 + e rounded
+// and c = e - (u - 1) its rounding error (u - 1 and c are exact; log_fast is
+// accurate relative to ln u near u = 1). c / u as c (2 - u): |c| <= 1.2e-16
+// and 1 / u - (2 - u) = (u - 1)^2 / u <= |e|, so what that leaves is below
+// 1.2e-16 |e| -- without a second reciprocal. Otherwise log q as before. One
+// log either way (selects, no branch).
+H3D_HD double log_quot(double num, double den, double d, bool near,
+                       const LogTab* tab) {
+  const double e = div_fast(near ? d : num, den);
+  const double u = near ? 1.0 + e : e;
+  const double corr = near ? (e - (u - 1.0)) * (2.0 - u) : 0.0;
+  return log_fast_checked(u, tab) + corr;
+}
+
 // Per-pixel LRT (lrt.py:7-50). a[k] = disp_wide[k] = disp[cond[k]]; CM is a
 // compile-time bound on the number of conditions C.
 template <int M, int CM, typename TX>
@@ -468,24 +490,32 @@ H3D_HD int lrt_pixel(const TX* x, const double* f, const double* a,
   // replicate -- and without the cancellation of two O(1e3) row sums that
   // leaves the reference's llr ~1e-13 of noise (the rows' rounding; the
   // p-values move by that only).
+  // (the logs through log_quot: by the difference mu0 - mu1 where the two
+  // means are within a factor of 2)
   double lq[CM];
+  bool near[CM];
 #pragma unroll
-  for (int c = 0; c < CM; ++c)
-    lq[c] = (c < C) ? log_fast_checked(div_fast(*mu0, mu1[c]), tab) : 0.0;
+  for (int c = 0; c < CM; ++c) {
+    near[c] = c < C && *mu0 >= 0.5 * mu1[c] && *mu0 <= 2.0 * mu1[c];
+    lq[c] = (c < C) ? log_quot(*mu0, mu1[c], *mu0 - mu1[c], near[c], tab) : 0.0;
+  }
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < M; ++k) {
     if (k < R) {
       double m1 = 0.0, l = 0.0;
+      bool nr = false;
 #pragma unroll
       for (int c = 0; c < CM; ++c)
         if (c == cond[k]) {
           m1 = mu1[c];
           l = lq[c];
+          nr = near[c];
         }
       const double xk = (double)x[k];
       const double r = 1.0 / a[k];
-      const double lr = log_fast_checked(div_fast(r + *mu0 * f[k], r + m1 * f[k]), tab);
+      const double lr = log_quot(r + *mu0 * f[k], r + m1 * f[k], (*mu0 - m1) * f[k],
+                                 nr, tab);
       acc += xk * l - (r + xk) * lr;
     }
   }

@@ -1267,12 +1267,28 @@ H3D_HD double chi2_sf(double df, double x);
 // closed-form paths they take otherwise
 H3D_HD_COLD double chi2_sf_cold(double df, double x) { return chi2_sf(df, x); }
 
+// Q(a, y) where igamc returned 0 because the prefactor's exponent ax = a ln y
+// - y - lgamma(a) is below -MAXLOG (cephes' rule, which igamc keeps for the
+// equalize pass): Q is still a subnormal double down to e^-745, and the
+// closed forms of df = 1 and 2 return it, so the general df must too (p of a
+// design of four or more conditions was 0 where p = 3.5e-314). The continued
+// fraction's ratio times e^(ax + 80 ln 2), a normal double, scaled by 2^-80:
+// one rounding into the subnormal range.
+H3D_HD_COLD double igamc_tiny(double a, double y) {
+  const double ax = a * log(y) - y - lgam(a);
+  if (!(ax > -800.0)) return 0.0;
+  return ldexp(igamc_cf_ratio(a, y) * exp(ax + 80.0 * 0.6931471805599453), -80);
+}
+
 H3D_HD double chi2_sf(double df, double x) {
   if (x != x) return NAN;
   if (x <= 0.0) return 1.0;
   if (df == 1.0) return erfc(sqrt(x / 2.0));
   if (df == 2.0) return exp(-x / 2.0);
-  return igamc(df / 2.0, x / 2.0);
+  const double a = df / 2.0, y = x / 2.0;
+  const double q = igamc(a, y);
+  if (q == 0.0 && a > 0.0 && y > a && y < 1e4) return igamc_tiny(a, y);
+  return q;
 }
 
 }  // namespace h3d

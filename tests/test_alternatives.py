@@ -9,6 +9,7 @@ and MME dispersions to ~1e-13, loop_idx bit-exact, identical calls."""
 import os
 import shutil
 import tempfile
+import warnings
 
 import numpy as np
 import pandas as pd
@@ -113,3 +114,108 @@ def test_poisson_lrt_refit_false_raises_like_reference():
         poisson_lrt(np.ones((3, 4), dtype=np.int64), np.ones((3, 4)),
                     np.array([[1, 0], [1, 0], [0, 1], [0, 1]], dtype=bool),
                     refit_mu=False)
+
+
+# ---- every k_lrt_poisson / k_mme_per_pixel instantiation ------------------
+
+EPS = 2.2e-16
+
+
+def _alt_inputs(R, C):
+    """n = 300 pixels: mu 1e-1 .. 1e3, f 0.1 .. 10, 20 % of the counts
+    zeroed (all-zero conditions and pixels included); the last condition has
+    a single replicate (MME: NaN), so (18, 2) has one of 17 (the pairwise
+    branch of np_sum_mask, >= 8 per condition) -- and a two-condition design
+    has one condition with an MME value, the other all NaN."""
+    rng = np.random.default_rng(100 * R + C)
+    n = 300
+    cond = np.r_[np.arange(C), rng.integers(0, C - 1, R - C)]
+    rng.shuffle(cond)
+    mu = 10 ** rng.uniform(-1, 3, (n, 1))
+    f = 10 ** rng.uniform(-1, 1, (n, R))
+    raw = rng.poisson(mu * f).astype(np.int64)
+    raw[rng.random((n, R)) < 0.2] = 0
+    design = np.eye(C, dtype=bool)[cond]
+    assert np.any(raw[:, design[:, 0]].sum(axis=1) == 0)
+    assert np.bincount(cond)[C - 1] == 1
+    return raw, f, cond.astype(np.int32), design
+
+
+@pytest.fixture(scope='module')
+def alt_ctx():
+    from hic3defdr_amd import _native
+    return _native.context(0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('R,C', [(4, 2), (4, 3), (7, 2), (8, 4), (12, 5),
+                                 (18, 2), (32, 8)])
+def test_poisson_lrt_instantiations_vs_oracle(alt_ctx, R, C):
+    """k_lrt_poisson<4,2>, <4,4>, <8,4> (R = 7 and 8), <16,8>, <32,8> (R = 18
+    and 32) against oracle.poisson_lrt. Means: 64 eps relative (positive-term
+    sums; a product may fuse into the sum). llr: (8 + R) eps sum_k (|x ln m| +
+    lgamma(x + 1) + m) over both rows. p: scipy's chi2.sf at the kernel's own
+    llr within igam_err's tolerance."""
+    import scipy.special as sc
+    import scipy.stats as stats
+    from test_special_host import igam_err
+    raw, f, cond, design = _alt_inputs(R, C)
+    if (R, C) == (18, 2):
+        assert np.bincount(cond).max() >= 8
+    p, llr, m0, m1 = alt_ctx.lrt_poisson(raw, f, cond, C)
+    with np.errstate(all='ignore'):
+        rp, rllr, rm0, rm1 = oracle.poisson_lrt(raw, f, design)
+    np.testing.assert_array_equal(np.isnan(m1), np.isnan(rm1))
+    assert not np.isnan(m0).any() and not np.isnan(llr).any()
+    e0, e1 = rel_err(m0, rm0), rel_err(m1, rm1)
+    x = raw.astype(float)
+    scale = np.zeros(len(raw))
+    for m in (rm0[:, None] * f, np.dot(rm1, design.T) * f):
+        with np.errstate(all='ignore'):
+            xl = np.where(x > 0, np.abs(x * np.log(m)), 0.0)
+        scale += (xl + sc.gammaln(x + 1) + m).sum(axis=1)
+    bound = (8 + R) * EPS * scale
+    tiny = bound == 0        # an all-zero pixel: llr = 0 exactly
+    assert np.all(llr[tiny] == rllr[tiny])
+    units = float(np.max(np.abs(llr - rllr)[~tiny] / bound[~tiny]))
+    x2 = -2 * llr
+    pos = x2 > 0
+    sf = stats.chi2.sf(x2, C - 1)
+    pos &= ~((sf == 0) & (p < 2.2250738585072014e-308))  # scipy flushes
+    perr = igam_err(p[pos], sf[pos], np.full(int(pos.sum()), (C - 1) / 2.0),
+                    x2[pos] / 2)
+    print('poisson R=%d C=%d mu0=%.3g mu1=%.3g (of 64 eps = %.3g) '
+          'llr=%.3g of its bound, p=%.3g of igam_err tol'
+          % (R, C, e0, e1, 64 * EPS, units, perr))
+    assert e0 <= 64 * EPS and e1 <= 64 * EPS
+    assert units <= 1
+    assert np.all(p[x2 <= 0] == 1.0)
+    assert perr < 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('R,C', [(4, 2), (7, 2), (18, 2)])
+def test_mme_per_pixel_instantiations_vs_oracle(alt_ctx, R, C):
+    """k_mme_per_pixel<4>, <8>, <32> against oracle.mme_per_pixel: the NaN
+    layout (a single-replicate condition, an all-zero condition) matches, and
+    |delta| <= 64 eps (var + m) / m^2."""
+    raw, f, cond, design = _alt_inputs(R, C)
+    got = alt_ctx.mme_per_pixel(raw.astype(np.float64), f, cond, C)
+    worst = 0.0
+    for c in range(C):
+        data = raw[:, design[:, c]] / f[:, design[:, c]]
+        with np.errstate(all='ignore'), warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)   # ddof = n = 1
+            ref = oracle.mme_per_pixel(data)
+            m = data.mean(axis=1)
+            bound = 64 * EPS * (data.var(axis=1, ddof=1) + m) / m ** 2
+        np.testing.assert_array_equal(np.isnan(got[:, c]), np.isnan(ref))
+        ok = ~np.isnan(ref)
+        if design[:, c].sum() == 1:
+            assert not ok.any()
+        else:
+            assert ok.sum() > 100
+            worst = max(worst, float(np.max(
+                np.abs(got[ok, c] - ref[ok]) / bound[ok])))
+    print('mme R=%d C=%d: %.3g of its bound' % (R, C, worst))
+    assert worst <= 1
