@@ -38,6 +38,8 @@ EXPORTS = [
     'h3d_pixel_f_dev', 'h3d_read_text_column', 'h3d_set_qcml_tol',
     'h3d_window_gather', 'h3d_window_gather_dev', 'h3d_stack_aggregate',
     'h3d_filter_sparse_rows', 'h3d_kr_balance',
+    'h3d_nb_fit_mu', 'h3d_nb_fit_mu_dev', 'h3d_nb_equalize',
+    'h3d_nb_equalize_dev', 'h3d_nb_quantile_map', 'h3d_nb_logpmf',
 ]
 
 
@@ -176,6 +178,16 @@ def load_library(path=None):
                                             _P, _P, _P, _P, _P]),
             'h3d_kr_balance': (_I, [_P, _P, _P, _P, _I, _I64, _I, _I, _D, _D,
                                     _D, _I, _P, _P, _P, _P, _P, _P, _I]),
+            'h3d_nb_fit_mu': (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _P,
+                                   _P]),
+            'h3d_nb_fit_mu_dev': (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I,
+                                       _P, _P]),
+            'h3d_nb_equalize': (_I, [_P, _P, _P, _D, _P, _I64, _I, _P, _P,
+                                     _P]),
+            'h3d_nb_equalize_dev': (_I, [_P, _P, _P, _D, _P, _I64, _I, _P, _P,
+                                         _P]),
+            'h3d_nb_quantile_map': (_I, [_P, _P, _P, _P, _D, _P, _I64, _P]),
+            'h3d_nb_logpmf': (_I, [_P, _P, _P, _P, _I64, _P]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -663,6 +675,126 @@ class Context(object):
             self.handle, d_raw, d_f, d_dist, d_table, n, R, C, _ptr(cond),
             D, int(bool(refit_mu)), d_p, d_llr, d_mu0, d_mu1, d_disp),
             'h3d_lrt_dev_tab')
+
+    # -- scaled NB operators (util/scaled_nb.py) ------------------------------
+    @staticmethod
+    def _alpha_strides(alpha, n, R):
+        """alpha as the four broadcast forms of fit_mu_hat
+        (scaled_nb.py:110-127) -> (contiguous values, pixel stride, replicate
+        stride), never a materialised (n, R) copy of a smaller form."""
+        a = np.asarray(alpha, dtype=np.float64)
+        if a.ndim == 0 or a.shape in ((1,), (1, 1)):
+            return _c(a.reshape(1), np.float64), 0, 0
+        if a.shape in ((R,), (1, R)):
+            return _c(a.reshape(R), np.float64), 0, 1
+        if a.shape == (n, 1):
+            return _c(a.reshape(n), np.float64), 1, 0
+        if a.shape == (n, R):
+            return _c(a, np.float64), R, 1
+        raise ValueError('alpha of shape %s does not broadcast against '
+                         '(%d, %d)' % (a.shape, n, R))
+
+    def nb_fit_mu(self, x, b, alpha):
+        """fit_mu_hat (scaled_nb.py:71-183) for x, b (n, R) and alpha in any
+        of its broadcast forms: (mu (n), flags). A failed pixel's mean is NaN
+        and its H3D_FLAG_* bits are in ``flags``."""
+        x = _c(x, np.int64)
+        b = _c(b, np.float64)
+        n, R = x.shape
+        if b.shape != (n, R):
+            raise ValueError('x and b must both be (n, R)')
+        a, spx, srep = self._alpha_strides(alpha, n, R)
+        mu = np.empty(n)
+        fl = _I(0)
+        _check(self.lib.h3d_nb_fit_mu(
+            self.handle, _ptr(x), _ptr(b), _ptr(a), spx, srep, n, R, _ptr(mu),
+            ctypes.byref(fl)), 'h3d_nb_fit_mu')
+        return mu, fl.value
+
+    def nb_fit_mu_dev(self, d_x, d_b, d_alpha, alpha_strides, n, R, d_mu):
+        """nb_fit_mu on device pointers (x int32, the rest float64);
+        ``alpha_strides`` = (pixel, replicate) element strides of d_alpha,
+        each 0 or the natural one. Returns the flags."""
+        fl = _I(0)
+        _check(self.lib.h3d_nb_fit_mu_dev(
+            self.handle, d_x, d_b, d_alpha, alpha_strides[0],
+            alpha_strides[1], n, R, d_mu, ctypes.byref(fl)),
+            'h3d_nb_fit_mu_dev')
+        return fl.value
+
+    def nb_equalize(self, x, f, alpha, want_mu=False):
+        """equalize (scaled_nb.py:186-214) for x, f (n, R) at a scalar alpha
+        or one per pixel (n,): (pseudodata (n, R), mu_hat (n) or None,
+        flags)."""
+        x = _c(x, np.int64)
+        f = _c(f, np.float64)
+        n, R = x.shape
+        if f.shape != (n, R):
+            raise ValueError('data and f must both be (n, R)')
+        a = np.asarray(alpha, dtype=np.float64)
+        if a.ndim == 0:
+            a_s, a_px = float(a), None
+        elif a.shape == (n,):
+            a_s, a_px = 0.0, _c(a, np.float64)
+        else:
+            raise ValueError('alpha must be a scalar or (n,)')
+        out = np.empty((n, R))
+        mu = np.empty(n) if want_mu else None
+        fl = _I(0)
+        _check(self.lib.h3d_nb_equalize(
+            self.handle, _ptr(x), _ptr(f), a_s, _ptr(a_px), n, R, _ptr(out),
+            _ptr(mu), ctypes.byref(fl)), 'h3d_nb_equalize')
+        return out, mu, fl.value
+
+    def nb_equalize_dev(self, d_x, d_f, alpha, n, R, d_pseudo, d_alpha_px=None,
+                        d_mu_hat=None):
+        """nb_equalize on device pointers (x int32, the rest float64); the
+        dispersion is ``alpha``, or per pixel from d_alpha_px. Returns the
+        flags."""
+        fl = _I(0)
+        _check(self.lib.h3d_nb_equalize_dev(
+            self.handle, d_x, d_f, float(alpha), d_alpha_px, n, R, d_pseudo,
+            d_mu_hat, ctypes.byref(fl)), 'h3d_nb_equalize_dev')
+        return fl.value
+
+    def nb_quantile_map(self, x, mu_in, mu_out, alpha):
+        """q2qnbinom (scaled_nb.py:217-275) over flat float64 arrays of one
+        length; alpha a scalar or one per element. ``mu_in`` / ``mu_out`` must
+        be contiguous float64 arrays: they are clamped in place, as the
+        reference does (:240-242)."""
+        x = _c(x, np.float64)
+        n = x.size
+        for m in (mu_in, mu_out):
+            if not (isinstance(m, np.ndarray) and m.dtype == np.float64 and
+                    m.flags.c_contiguous and m.flags.writeable and
+                    m.size == n):
+                raise ValueError('mu_in / mu_out must be writable contiguous '
+                                 'float64 arrays of x\'s size')
+        a = np.asarray(alpha, dtype=np.float64)
+        if a.ndim == 0:
+            a_s, a_el = float(a), None
+        elif a.size == n:
+            a_s, a_el = 0.0, _c(a, np.float64)
+        else:
+            raise ValueError('alpha must be a scalar or one per element')
+        out = np.empty(x.shape)
+        _check(self.lib.h3d_nb_quantile_map(
+            self.handle, _ptr(x), _ptr(mu_in), _ptr(mu_out), a_s, _ptr(a_el),
+            n, _ptr(out)), 'h3d_nb_quantile_map')
+        return out
+
+    def nb_logpmf(self, k, m, phi):
+        """logpmf (scaled_nb.py:12-33) over float64 arrays of one shape."""
+        k = _c(k, np.float64)
+        m = _c(m, np.float64)
+        phi = _c(phi, np.float64)
+        if not (k.shape == m.shape == phi.shape):
+            raise ValueError('k, m and phi must have one shape')
+        out = np.empty(k.shape)
+        _check(self.lib.h3d_nb_logpmf(self.handle, _ptr(k), _ptr(m),
+                                      _ptr(phi), k.size, _ptr(out)),
+               'h3d_nb_logpmf')
+        return out
 
     # -- alternative models (analysis/alternatives.py) -----------------------
     def lrt_poisson(self, raw, f, cond_of_rep, C):

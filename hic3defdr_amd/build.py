@@ -2,7 +2,8 @@
 
 - ``libh3d.so``          the product: C-ABI host code + gfx950 HIP kernels
                           (csrc/h3d_api.hip, h3d_alt.hip, h3d_balance.hip,
-                          h3d_calls.cpp, h3d_npz.cpp; links zlib), loaded
+                          h3d_nb.hip, h3d_calls.cpp, h3d_npz.cpp; links
+                          zlib), loaded
                           by hic3defdr_amd._native.
 - ``libh3d_hosttest.so`` the device numerics compiled for the host, used only
                           by CPU unit tests (tests/test_special_host.py).
@@ -40,6 +41,7 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_prepare_api.hip', 'hipcc'), ('h3d_alt.hip', 'hipcc'),
                ('h3d_bh.hip', 'hipcc'), ('h3d_table.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
+               ('h3d_nb.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]
 HEADERS = ['h3d_special.h', 'h3d_model.h', 'h3d_kernels.h', 'h3d_host.h',
            'h3d_prepare.h', 'h3d_errors.h', 'h3d_ctx.h', 'h3d_lrt_group.h', 'h3d_logtab.h']
@@ -48,6 +50,10 @@ HEADERS = ['h3d_special.h', 'h3d_model.h', 'h3d_kernels.h', 'h3d_host.h',
 JOBS = max(1, min(int(os.environ.get('MAX_JOBS', '8')), os.cpu_count() or 1))
 HIP_FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC',
              '-munsafe-fp-atomics']
+# per-TU flags. h3d_nb.hip: every device function inlined -- with calls, the
+# frame of the out-of-line find_inverse_gamma (one callee-saved VGPR) gave
+# each k_nb_equalize / k_nb_quantile_map 16 B of scratch
+TU_FLAGS = {'h3d_nb.hip': ['-mllvm', '-amdgpu-function-calls=false']}
 
 
 def _digest(cmd, deps):
@@ -121,8 +127,8 @@ def _native_objects(objdir=None, extra=()):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src + '.o')
         if cc == 'hipcc':
-            cmd = [HIPCC] + HIP_FLAGS + list(extra) + ['-I', INC, '-c', '-o',
-                                                       o, s]
+            cmd = [HIPCC] + HIP_FLAGS + TU_FLAGS.get(src, []) + list(extra) \
+                + ['-I', INC, '-c', '-o', o, s]
         else:
             cmd = ['g++', '-O2', '-std=c++17', '-fPIC', '-I', INC, '-c', '-o',
                    o, s]

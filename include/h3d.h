@@ -18,6 +18,10 @@
  *   h3d_lrt                <- util/lrt.py:7-50 (+ analysis/analysis.py:272-278)
  *   h3d_lrt_wide           <- util/lrt.py:7 lrt(raw, f, disp, design) as called
  *   h3d_cml                <- util/dispersion.py:46-80 cml
+ *   h3d_nb_fit_mu / _dev   <- util/scaled_nb.py:71-183 fit_mu_hat
+ *   h3d_nb_equalize / _dev <- util/scaled_nb.py:186-214 equalize
+ *   h3d_nb_quantile_map    <- util/scaled_nb.py:217-275 q2qnbinom
+ *   h3d_nb_logpmf          <- util/scaled_nb.py:12-33 logpmf
  *   h3d_bh / _ctx / _dev   <- analysis/analysis.py:286-303 (lib5c
  *                              adjust_pvalues = BH)
  *   h3d_find_clusters      <- util/clusters.py:73-97 find_clusters (threshold /
@@ -349,6 +353,60 @@ int h3d_lrt_wide(h3d_ctx* ctx, const int64_t* raw, const double* f,
  * k_brent search); *disp = delta / (1 - delta). H3D_ENOCONV where the
  * reference's assert res.success would fail. */
 int h3d_cml(h3d_ctx* ctx, const double* data, int64_t n, int r, double* disp);
+
+/* ---- scaled NB operators (util/scaled_nb.py) ---------------------------- */
+
+/* The functions dispersion.qcml and lrt.lrt import (dispersion.py:5,
+ * lrt.py:4), one lane per pixel in the caller's pixel order, replicate-minor
+ * (n, R) rows, 1 <= R <= 32 (H3D_EINPUT otherwise). A pixel's failure does
+ * not fail the call: the H3D_FLAG_* bits of every pixel are OR-ed into
+ * *flags (may be NULL), the return code stays 0, and that pixel's outputs are
+ * NaN -- the caller raises what the reference raises. Host entries upload,
+ * launch and download (counts int64, H3D_EINPUT outside [0, 2^31)); the _dev
+ * entries take device pointers (counts int32) on the ctx's stream and wait
+ * for it only to read the flags. n = 0 launches nothing. */
+
+/* scaled_nb.py:71-183 fit_mu_hat: mu (n) = the MLE of the mean under fixed
+ * dispersions. alpha is read at alpha[i * alpha_px_stride + k *
+ * alpha_rep_stride] and holds only the values so addressed: the reference's
+ * broadcast forms (:110-127) scalar (0, 0), (R,) (0, 1), (n, 1) (1, 0) and
+ * (n, R) (R, 1); other strides are H3D_EARG. H3D_FLAG_BADIN: the asserts of
+ * :139-141; H3D_FLAG_NOROOT: an all-zero row (the brentq fallback's
+ * ValueError, :172-181); H3D_FLAG_NOCONV: the solver's step limit. */
+int h3d_nb_fit_mu(h3d_ctx* ctx, const int64_t* x, const double* b,
+                  const double* alpha, int64_t alpha_px_stride,
+                  int64_t alpha_rep_stride, int64_t n, int R, double* mu,
+                  int* flags);
+int h3d_nb_fit_mu_dev(h3d_ctx* ctx, const int32_t* d_x, const double* d_b,
+                      const double* d_alpha, int64_t alpha_px_stride,
+                      int64_t alpha_rep_stride, int64_t n, int R, double* d_mu,
+                      int* flags);
+
+/* scaled_nb.py:186-214 equalize: pseudo (n, R) from counts x and factors f at
+ * the dispersion alpha, or at alpha_px[i] per pixel when alpha_px is not NULL
+ * (the reference's code takes that form too: q2qnbinom's alpha is "one per
+ * x", :230-232). The clamp of mu_out at 0.25 carries from one replicate into
+ * the next as the reference's in-place update does (:209-213, :240-242).
+ * mu_hat (n), optional: the fitted means (:208). Flags as h3d_nb_fit_mu. */
+int h3d_nb_equalize(h3d_ctx* ctx, const int64_t* x, const double* f,
+                    double alpha, const double* alpha_px, int64_t n, int R,
+                    double* pseudo, double* mu_hat, int* flags);
+int h3d_nb_equalize_dev(h3d_ctx* ctx, const int32_t* d_x, const double* d_f,
+                        double alpha, const double* d_alpha_px, int64_t n,
+                        int R, double* d_pseudo, double* d_mu_hat, int* flags);
+
+/* scaled_nb.py:217-275 q2qnbinom, elementwise over n values: out[i] = x[i]
+ * carried from NB(mu_in[i]) to NB(mu_out[i]) at the dispersion alpha, or
+ * alpha_el[i] when alpha_el is not NULL. mu_in / mu_out are read AND
+ * written: where either is below 0.25 both come back as 0.25, as the
+ * reference mutates its arguments (:240-242). */
+int h3d_nb_quantile_map(h3d_ctx* ctx, const double* x, double* mu_in,
+                        double* mu_out, double alpha, const double* alpha_el,
+                        int64_t n, double* out);
+
+/* scaled_nb.py:12-33 logpmf, elementwise over n values of k, m, phi. */
+int h3d_nb_logpmf(h3d_ctx* ctx, const double* k, const double* m,
+                  const double* phi, int64_t n, double* out);
 
 /* ---- bh ---------------------------------------------------------------- */
 
