@@ -40,6 +40,10 @@ EXPORTS = [
     'h3d_filter_sparse_rows', 'h3d_kr_balance',
     'h3d_nb_fit_mu', 'h3d_nb_fit_mu_dev', 'h3d_nb_equalize',
     'h3d_nb_equalize_dev', 'h3d_nb_quantile_map', 'h3d_nb_logpmf',
+    'h3d_group_sums', 'h3d_group_sums_dev', 'h3d_histogram',
+    'h3d_histogram_dev', 'h3d_ma_stats', 'h3d_density_grid',
+    'h3d_rank_average', 'h3d_corr_matrix', 'h3d_pixel_moments',
+    'h3d_balance_pixels',
 ]
 
 
@@ -188,6 +192,19 @@ def load_library(path=None):
                                          _P]),
             'h3d_nb_quantile_map': (_I, [_P, _P, _P, _P, _D, _P, _I64, _P]),
             'h3d_nb_logpmf': (_I, [_P, _P, _P, _P, _I64, _P]),
+            'h3d_group_sums': (_I, [_P, _P, _P, _I64, _I, _I, _P, _P]),
+            'h3d_group_sums_dev': (_I, [_P, _P, _P, _I64, _I, _I, _P, _P]),
+            'h3d_histogram': (_I, [_P, _P, _I64, _P, _I, _P]),
+            'h3d_histogram_dev': (_I, [_P, _P, _I64, _P, _I, _P]),
+            'h3d_ma_stats': (_I, [_P, _P, _I64, _I, _I, _P, _I, _I, _P, _P,
+                                  _I64, _D, _P, _P, _P, _P]),
+            'h3d_density_grid': (_I, [_P, _P, _P, _P, _I64, _I, _P, _I, _P,
+                                      _I, _P]),
+            'h3d_rank_average': (_I, [_P, _P, _I64, _I, _P, _P]),
+            'h3d_corr_matrix': (_I, [_P, _P, _I64, _I, _I, _P]),
+            'h3d_pixel_moments': (_I, [_P, _P, _I64, _I, _P, _I, _P, _P]),
+            'h3d_balance_pixels': (_I, [_P, _P, _P, _P, _P, _I64, _I, _I,
+                                        _P]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -794,6 +811,148 @@ class Context(object):
         _check(self.lib.h3d_nb_logpmf(self.handle, _ptr(k), _ptr(m),
                                       _ptr(phi), k.size, _ptr(out)),
                'h3d_nb_logpmf')
+        return out
+
+    # -- diagnostics (util/diagnostics.py) -----------------------------------
+    def group_sums(self, keys, values, K):
+        """(sums (K, C), counts (K) int64) of the rows of ``values`` (n, C)
+        grouped by ``keys`` (n) in [0, K); a negative key drops its row
+        (h3d_group_sums). The sums have a fixed order."""
+        keys = _c(keys, np.int32)
+        values = _c(values, np.float64)
+        if values.ndim != 2 or keys.shape != (values.shape[0],):
+            raise ValueError('values must be (n, C) and keys (n,)')
+        n, C = values.shape
+        sums = np.empty((K, C), dtype=np.float64)
+        counts = np.empty(K, dtype=np.int64)
+        _check(self.lib.h3d_group_sums(self.handle, _ptr(keys), _ptr(values),
+                                       n, int(K), C, _ptr(sums),
+                                       _ptr(counts)), 'h3d_group_sums')
+        return sums, counts
+
+    def group_sums_dev(self, keys, values, K):
+        """group_sums on torch tensors of this ctx's device: ``keys`` (n)
+        int32, ``values`` (n, C) float64; returns tensors (sums, counts)."""
+        import torch
+        if keys.dtype != torch.int32 or values.dtype != torch.float64 or \
+                values.dim() != 2 or tuple(keys.shape) != (values.shape[0],):
+            raise ValueError('keys must be int32 (n,), values float64 (n, C)')
+        keys, values = keys.contiguous(), values.contiguous()
+        n, C = values.shape
+        sums = torch.empty((K, C), dtype=torch.float64, device=values.device)
+        counts = torch.empty(K, dtype=torch.int64, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()
+        _check(self.lib.h3d_group_sums_dev(
+            self.handle, _P(keys.data_ptr()), _P(values.data_ptr()), n,
+            int(K), C, _P(sums.data_ptr()), _P(counts.data_ptr())),
+            'h3d_group_sums_dev')
+        return sums, counts
+
+    def histogram(self, values, edges):
+        """np.histogram(values, bins=edges)[0] (h3d_histogram)."""
+        values = _c(values, np.float64).reshape(-1)
+        edges = _c(edges, np.float64)
+        counts = np.empty(max(len(edges) - 1, 0), dtype=np.int64)
+        _check(self.lib.h3d_histogram(self.handle, _ptr(values), len(values),
+                                      _ptr(edges), len(edges), _ptr(counts)),
+               'h3d_histogram')
+        return counts
+
+    def histogram_dev(self, values, edges):
+        """histogram of a float64 torch tensor on this ctx's device; the
+        edges stay on the host. Returns an int64 tensor."""
+        import torch
+        if values.dtype != torch.float64:
+            raise ValueError('values must be float64')
+        values = values.contiguous().reshape(-1)
+        edges = _c(edges, np.float64)
+        counts = torch.empty(max(len(edges) - 1, 0), dtype=torch.int64,
+                             device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()
+        _check(self.lib.h3d_histogram_dev(
+            self.handle, _P(values.data_ptr()), values.numel(), _ptr(edges),
+            len(edges), _P(counts.data_ptr())), 'h3d_histogram_dev')
+        return counts
+
+    def ma_stats(self, scaled, cond_of_rep, C, cond0, cond1, qvalues, fdr,
+                 loop_idx=None):
+        """(mean (n, 2), m, a, label int8) of h3d_ma_stats."""
+        scaled = _c(scaled, np.float64)
+        cond = _c(cond_of_rep, np.int32)
+        q = _c(qvalues, np.float64)
+        n, R = scaled.shape
+        loop = _c(loop_idx, np.uint8) if loop_idx is not None else None
+        mean = np.empty((n, 2))
+        m, a = np.empty(n), np.empty(n)
+        label = np.empty(n, dtype=np.int8)
+        _check(self.lib.h3d_ma_stats(
+            self.handle, _ptr(scaled), n, R, int(C), _ptr(cond), int(cond0),
+            int(cond1), _ptr(loop), _ptr(q), len(q), float(fdr), _ptr(mean),
+            _ptr(m), _ptr(a), _ptr(label)), 'h3d_ma_stats')
+        return mean, m, a, label
+
+    def density_grid(self, x, y, label, n_classes, xedges, yedges):
+        """counts (L, Ex - 1, Ey - 1) int64 of h3d_density_grid."""
+        x, y = _c(x, np.float64), _c(y, np.float64)
+        label = _c(label, np.int8)
+        xe, ye = _c(xedges, np.float64), _c(yedges, np.float64)
+        counts = np.empty((int(n_classes), max(len(xe) - 1, 0),
+                           max(len(ye) - 1, 0)), dtype=np.int64)
+        _check(self.lib.h3d_density_grid(
+            self.handle, _ptr(x), _ptr(y), _ptr(label), len(x),
+            int(n_classes), _ptr(xe), len(xe), _ptr(ye), len(ye),
+            _ptr(counts)), 'h3d_density_grid')
+        return counts
+
+    def rank_average(self, columns):
+        """(ranks (R, n), nan flags (R)) of the rows of ``columns`` (R, n)
+        (h3d_rank_average)."""
+        v = _c(columns, np.float64)
+        R, n = v.shape
+        ranks = np.empty((R, n))
+        flags = np.zeros(R, dtype=np.int32)
+        _check(self.lib.h3d_rank_average(self.handle, _ptr(v), n, R,
+                                         _ptr(ranks), _ptr(flags)),
+               'h3d_rank_average')
+        return ranks, flags
+
+    def corr_matrix(self, columns, ranked=False):
+        """(R, R) Pearson matrix of the rows of ``columns`` (R, n), of their
+        average ranks with ``ranked`` (h3d_corr_matrix)."""
+        v = _c(columns, np.float64)
+        R, n = v.shape
+        out = np.empty((R, R))
+        _check(self.lib.h3d_corr_matrix(self.handle, _ptr(v), n, R,
+                                        int(bool(ranked)), _ptr(out)),
+               'h3d_corr_matrix')
+        return out
+
+    def pixel_moments(self, scaled, reps):
+        """(mean, var ddof=1) per pixel over the columns ``reps`` of
+        ``scaled`` (n, R) (h3d_pixel_moments)."""
+        scaled = _c(scaled, np.float64)
+        reps = _c(reps, np.int32)
+        n, R = scaled.shape
+        mean, var = np.empty(n), np.empty(n)
+        _check(self.lib.h3d_pixel_moments(self.handle, _ptr(scaled), n, R,
+                                          _ptr(reps), len(reps), _ptr(mean),
+                                          _ptr(var)), 'h3d_pixel_moments')
+        return mean, var
+
+    def balance_pixels(self, row, col, raw, bias):
+        """raw / (bias[row] * bias[col]) per replicate (h3d_balance_pixels):
+        raw (n, R) integers, bias (n_bins, R)."""
+        row, col = _c(row, np.int32), _c(col, np.int32)
+        raw = _c(raw, np.int64)
+        bias = _c(bias, np.float64)
+        n, R = raw.shape
+        if bias.ndim != 2 or bias.shape[1] != R or row.shape != (n,) or \
+                col.shape != (n,):
+            raise ValueError('raw (n, R), bias (n_bins, R), row and col (n,)')
+        out = np.empty((n, R))
+        _check(self.lib.h3d_balance_pixels(
+            self.handle, _ptr(row), _ptr(col), _ptr(raw), _ptr(bias), n, R,
+            bias.shape[0], _ptr(out)), 'h3d_balance_pixels')
         return out
 
     # -- alternative models (analysis/alternatives.py) -----------------------

@@ -40,6 +40,21 @@
  *   h3d_filter_sparse_rows <- util/filtering.py:8-33 filter_sparse_rows_count
  *   h3d_kr_balance         <- util/balancing.py:5-208 kr_balance (behind the
  *                              filter: README.md:602-614)
+ *   h3d_group_sums / _dev  <- plotting/distance_dependence.py:34-43 (the sums
+ *                              per distance bin), plotting/dispersion.py:133-144,
+ *                              :182-183 (the means per distance)
+ *   h3d_histogram / _dev   <- plotting/histograms.py (plt.hist = np.histogram;
+ *                              analysis/plotting.py:200-249)
+ *   h3d_ma_stats           <- analysis/plotting.py:307, plotting/ma.py:71-72,
+ *                              :131-155 (means, M, A, the series of each pixel)
+ *   h3d_density_grid       <- the ax.scatter_density calls of plotting/ma.py
+ *                              as per-class np.histogram2d counts
+ *   h3d_rank_average       <- scipy.stats.rankdata under spearmanr
+ *                              (analysis/plotting.py:369-376)
+ *   h3d_corr_matrix        <- scipy.stats.pearsonr / spearmanr over replicate
+ *                              pairs (analysis/plotting.py:369-376)
+ *   h3d_pixel_moments      <- analysis/plotting.py:128-129 np.mean / np.var
+ *   h3d_balance_pixels     <- analysis/plotting.py:46-48 balanced
  *
  * Conventions: 0 on success, a negative H3D_E* code otherwise (the message is
  * in h3d_last_error(), thread-local). Host buffers are C-contiguous and owned
@@ -595,6 +610,97 @@ int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                    const double* x0, double* bias_out, double* balanced_out,
                    int64_t* stats, int32_t* hist_inner, double* hist_norm,
                    int hist_cap);
+
+/* ---- diagnostics: the numbers under the reference's plot_* methods -------- */
+
+/* Every floating-point sum below has one fixed association (lane-strided
+ * running sums, an LDS tree, per-block partials, a final pass): a rerun,
+ * another launch grid and another ctx give the same bits. No floating-point
+ * atomics; counts are integer atomics. n < 2^31 throughout. */
+
+/* sums (K, C) and counts (K) int64 of the rows of values (n, C) row-major
+ * grouped by keys (n) int32: a key outside [0, K) drops its row. The members
+ * of a key are added in their original order (a stable sort of (key, index),
+ * then 16 interleaved slices per key). A key without rows gives 0; a NaN or
+ * an infinity stays in its own (key, column) cell. Replaces the per-bin
+ * boolean masks of plotting/distance_dependence.py:38-43 and
+ * plotting/dispersion.py:138, :182. K <= 4096, C <= 64. _dev: every array is
+ * a device pointer; synchronous. */
+int h3d_group_sums(h3d_ctx* ctx, const int32_t* keys, const double* values,
+                   int64_t n, int K, int C, double* sums, int64_t* counts);
+int h3d_group_sums_dev(h3d_ctx* ctx, const int32_t* d_keys,
+                       const double* d_values, int64_t n, int K, int C,
+                       double* d_sums, int64_t* d_counts);
+
+/* np.histogram(values, bins=edges): counts (E - 1) int64, bin i =
+ * [e_i, e_i+1), the last bin closed on the right, NaN and values outside
+ * [e_0, e_E-1] dropped. The bin is found by comparing against the edges
+ * themselves (binary search), so a value equal to an edge lands where numpy
+ * puts it. edges (E <= 4097) finite and strictly increasing, on the host in
+ * both forms; _dev: values and counts are device pointers. */
+int h3d_histogram(h3d_ctx* ctx, const double* values, int64_t n,
+                  const double* edges, int E, int64_t* counts);
+int h3d_histogram_dev(h3d_ctx* ctx, const double* d_values, int64_t n,
+                      const double* edges, int E, int64_t* d_counts);
+
+/* The MA plot's numbers for scaled (n, R): mean (n, 2) = the sum over the
+ * replicates of conditions cond0 / cond1 (design order) over their count
+ * (analysis/plotting.py:307), m = log2(mean0) - log2(mean1), a =
+ * 0.5 (log2(mean0) + log2(mean1)) (plotting/ma.py:71-72), and label (n) int8:
+ * 0 a non-loop pixel, 1 a loop pixel with !(q < fdr) (a NaN q too), 2
+ * significant and m > 0, 3 significant and m < 0, -1 significant with m == 0
+ * or NaN -- the pixels the reference draws in no series (ma.py:146-155).
+ * loop_idx (n) bytes, or NULL: every pixel is a loop pixel. qvalues (n_q): one
+ * per loop pixel in order; the pixel -> q-value index is the exclusive scan
+ * of loop_idx, done on the device. H3D_EARG: n_q differs from the loop
+ * pixels, a condition outside [0, C). Host buffers. */
+int h3d_ma_stats(h3d_ctx* ctx, const double* scaled, int64_t n, int R, int C,
+                 const int32_t* cond_of_rep, int cond0, int cond1,
+                 const uint8_t* loop_idx, const double* qvalues, int64_t n_q,
+                 double fdr, double* mean, double* m, double* a,
+                 int8_t* label);
+
+/* counts (L, Ex - 1, Ey - 1) int64: np.histogram2d(x, y, bins=[xedges,
+ * yedges])[0] of the points of each class label (n) int8 in [0, L); a row
+ * with another label, a NaN or an infinite coordinate is dropped. Each axis
+ * has h3d_histogram's edge rules. L <= 127, L (Ex - 1) (Ey - 1) < 2^28. Host
+ * buffers. */
+int h3d_density_grid(h3d_ctx* ctx, const double* x, const double* y,
+                     const int8_t* label, int64_t n, int L,
+                     const double* xedges, int Ex, const double* yedges,
+                     int Ey, int64_t* counts);
+
+/* scipy.stats.rankdata(method='average') of each of the R columns of n
+ * (values[c * n + i]): ranks, 1-based, ties share the mean of their ranks;
+ * -0.0 and +0.0 are one value. nan_flags (R): 1 where the column holds a NaN;
+ * its ranks are all NaN. R <= 32. Host buffers. */
+int h3d_rank_average(h3d_ctx* ctx, const double* values, int64_t n, int R,
+                     double* ranks, int32_t* nan_flags);
+
+/* corr (R, R): the Pearson correlation of every pair of the R columns of n,
+ * centred (column means, sums of products of deviations, s_ij /
+ * sqrt(s_ii s_jj), clipped to [-1, 1]; exactly symmetric). ranked != 0: of
+ * the columns' average ranks instead (Spearman). A column with a NaN and a
+ * constant column give NaN in their row and column, as scipy.stats.pearsonr
+ * / spearmanr do. R <= 32. Host buffers. */
+int h3d_corr_matrix(h3d_ctx* ctx, const double* values, int64_t n, int R,
+                    int ranked, double* corr);
+
+/* mean (n) and var (n) over the n_reps replicates reps[] of scaled (n, R):
+ * np.mean(x, axis=1) and np.var(x, ddof=1, axis=1) in numpy's two passes and
+ * its row-sum association (analysis/plotting.py:128-129); one replicate
+ * gives var = NaN (0 / 0). Host buffers. */
+int h3d_pixel_moments(h3d_ctx* ctx, const double* scaled, int64_t n, int R,
+                      const int32_t* reps, int n_reps, double* mean,
+                      double* var);
+
+/* balanced (n, R) = raw[i, r] / (bias[row[i], r] * bias[col[i], r])
+ * (analysis/plotting.py:46-48): a zero bias gives inf or NaN as numpy's
+ * division does. raw (n, R) int64, bias (n_bins, R); a row or col outside
+ * [0, n_bins) gives NaN. Host buffers. */
+int h3d_balance_pixels(h3d_ctx* ctx, const int32_t* row, const int32_t* col,
+                       const int64_t* raw, const double* bias, int64_t n,
+                       int R, int n_bins, double* balanced);
 
 /* ---- measurement -------------------------------------------------------- */
 
