@@ -44,6 +44,8 @@ EXPORTS = [
     'h3d_histogram_dev', 'h3d_ma_stats', 'h3d_density_grid',
     'h3d_rank_average', 'h3d_corr_matrix', 'h3d_pixel_moments',
     'h3d_balance_pixels',
+    'h3d_pixel_membership', 'h3d_pixel_membership_dev', 'h3d_roc_curve',
+    'h3d_roc_curve_dev', 'h3d_order_stats', 'h3d_bin_fractions',
 ]
 
 
@@ -205,6 +207,17 @@ def load_library(path=None):
             'h3d_pixel_moments': (_I, [_P, _P, _I64, _I, _P, _I, _P, _P]),
             'h3d_balance_pixels': (_I, [_P, _P, _P, _P, _P, _I64, _I, _I,
                                         _P]),
+            'h3d_pixel_membership': (_I, [_P, _P, _P, _I64, _P, _P, _I64,
+                                          _P]),
+            'h3d_pixel_membership_dev': (_I, [_P, _P, _P, _I64, _P, _P, _I64,
+                                              _P]),
+            'h3d_roc_curve': (_I, [_P, _P, _P, _I64, _I64, _I, _I, _P, _P, _P,
+                                   _P, _P, _P, _P, _P]),
+            'h3d_roc_curve_dev': (_I, [_P, _P, _P, _I64, _I64, _I, _I, _P, _P,
+                                       _P, _P, _P, _P, _P, _P]),
+            'h3d_order_stats': (_I, [_P, _P, _I64, _P, _I, _P, _P]),
+            'h3d_bin_fractions': (_I, [_P, _P, _P, _I64, _P, _P, _I, _D, _P,
+                                       _P]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -954,6 +967,122 @@ class Context(object):
             self.handle, _ptr(row), _ptr(col), _ptr(raw), _ptr(bias), n, R,
             bias.shape[0], _ptr(out)), 'h3d_balance_pixels')
         return out
+
+    # -- evaluation (util/evaluation.py, util/clusters.py) --------------------
+    def pixel_membership(self, row, col, prow, pcol):
+        """bool (n): (row[i], col[i]) in the pixel set {(prow, pcol)}
+        (h3d_pixel_membership); int64 host arrays."""
+        row, col = _c(row, np.int64), _c(col, np.int64)
+        prow, pcol = _c(prow, np.int64), _c(pcol, np.int64)
+        if row.ndim != 1 or col.shape != row.shape or prow.ndim != 1 or \
+                pcol.shape != prow.shape:
+            raise ValueError('row, col (n,) and prow, pcol (k,)')
+        out = np.zeros(len(row), dtype=np.uint8)
+        _check(self.lib.h3d_pixel_membership(
+            self.handle, _ptr(row), _ptr(col), len(row), _ptr(prow),
+            _ptr(pcol), len(prow), _ptr(out)), 'h3d_pixel_membership')
+        return out.view(np.bool_)
+
+    def pixel_membership_dev(self, row, col, prow, pcol):
+        """pixel_membership on int64 torch tensors of this ctx's device;
+        returns a bool tensor."""
+        import torch
+        for t in (row, col, prow, pcol):
+            if t.dtype != torch.int64 or t.dim() != 1:
+                raise ValueError('row, col, prow, pcol must be int64 (n,)')
+        if col.shape != row.shape or pcol.shape != prow.shape:
+            raise ValueError('row, col (n,) and prow, pcol (k,)')
+        row, col = row.contiguous(), col.contiguous()
+        prow, pcol = prow.contiguous(), pcol.contiguous()
+        out = torch.zeros(row.numel(), dtype=torch.uint8, device=row.device)
+        torch.cuda.current_stream(row.device).synchronize()
+        _check(self.lib.h3d_pixel_membership_dev(
+            self.handle, _P(row.data_ptr()), _P(col.data_ptr()), row.numel(),
+            _P(prow.data_ptr()), _P(pcol.data_ptr()), prow.numel(),
+            _P(out.data_ptr())), 'h3d_pixel_membership_dev')
+        return out.to(torch.bool)
+
+    ROC_FIELDS = ('fdr', 'fpr', 'tpr', 'thresh', 'fps', 'tps')
+
+    def roc_curve(self, labels, scores, n_fdr_points=100,
+                  drop_intermediate=True, complement=False):
+        """(dict of ROC_FIELDS -> (m,) arrays, flags) of h3d_roc_curve:
+        ``labels`` (n) bool / bytes, ``scores`` (n) float64; ``complement``:
+        the score is ``1 - scores``, formed on the device. flags has
+        H3D_FLAG_BADIN (16) when a score is NaN."""
+        labels = _c(labels, np.uint8)
+        scores = _c(scores, np.float64)
+        if labels.ndim != 1 or scores.shape != labels.shape:
+            raise ValueError('labels and scores must be (n,)')
+        n = len(labels)
+        out = [np.empty(n + 1, dtype=np.float64) for _ in range(4)] + \
+            [np.empty(n + 1, dtype=np.int64) for _ in range(2)]
+        m, fl = _I64(0), _I(0)
+        _check(self.lib.h3d_roc_curve(
+            self.handle, _ptr(labels), _ptr(scores), n, int(n_fdr_points),
+            int(bool(drop_intermediate)), int(bool(complement)),
+            *([_ptr(a) for a in out] + [ctypes.byref(m), ctypes.byref(fl)])),
+            'h3d_roc_curve')
+        return (dict((k, a[:m.value].copy())
+                     for k, a in zip(self.ROC_FIELDS, out)), fl.value)
+
+    def roc_curve_dev(self, labels, scores, n_fdr_points=100,
+                      drop_intermediate=True, complement=False):
+        """roc_curve on torch tensors of this ctx's device: ``labels`` (n)
+        uint8 or bool, ``scores`` (n) float64; the dict holds tensors."""
+        import torch
+        if labels.dtype == torch.bool:
+            labels = labels.to(torch.uint8)
+        if labels.dtype != torch.uint8 or scores.dtype != torch.float64 or \
+                labels.dim() != 1 or scores.shape != labels.shape:
+            raise ValueError('labels must be uint8 / bool (n,), scores '
+                             'float64 (n,)')
+        labels, scores = labels.contiguous(), scores.contiguous()
+        n = labels.numel()
+        out = [torch.empty(n + 1, dtype=torch.float64, device=scores.device)
+               for _ in range(4)] + \
+            [torch.empty(n + 1, dtype=torch.int64, device=scores.device)
+             for _ in range(2)]
+        m, fl = _I64(0), _I(0)
+        torch.cuda.current_stream(scores.device).synchronize()
+        _check(self.lib.h3d_roc_curve_dev(
+            self.handle, _P(labels.data_ptr()), _P(scores.data_ptr()), n,
+            int(n_fdr_points), int(bool(drop_intermediate)),
+            int(bool(complement)),
+            *([_P(a.data_ptr()) for a in out] +
+              [ctypes.byref(m), ctypes.byref(fl)])), 'h3d_roc_curve_dev')
+        return (dict((k, a[:m.value].clone())
+                     for k, a in zip(self.ROC_FIELDS, out)), fl.value)
+
+    def order_stats(self, values, ranks):
+        """(the values at the 0-based ``ranks`` of ``values`` sorted
+        ascending, NaN last; the NaN count) of h3d_order_stats."""
+        values = _c(values, np.float64).reshape(-1)
+        ranks = _c(ranks, np.int64).reshape(-1)
+        out = np.empty(len(ranks), dtype=np.float64)
+        nan = _I64(0)
+        _check(self.lib.h3d_order_stats(
+            self.handle, _ptr(values), len(values), _ptr(ranks), len(ranks),
+            _ptr(out), ctypes.byref(nan)), 'h3d_order_stats')
+        return out, nan.value
+
+    def bin_fractions(self, p, dist, lo, hi, p_star):
+        """(members, below) int64 (B) of h3d_bin_fractions: per inclusive
+        range [lo[b], hi[b]] of ``dist`` the pixels, and those of them with
+        ``p < p_star``."""
+        p = _c(p, np.float64)
+        dist = _c(dist, np.int64)
+        lo, hi = _c(lo, np.int64), _c(hi, np.int64)
+        if p.ndim != 1 or dist.shape != p.shape or lo.ndim != 1 or \
+                hi.shape != lo.shape:
+            raise ValueError('p, dist (n,) and lo, hi (B,)')
+        members = np.zeros(len(lo), dtype=np.int64)
+        below = np.zeros(len(lo), dtype=np.int64)
+        _check(self.lib.h3d_bin_fractions(
+            self.handle, _ptr(p), _ptr(dist), len(p), _ptr(lo), _ptr(hi),
+            len(lo), float(p_star), _ptr(members), _ptr(below)),
+            'h3d_bin_fractions')
+        return members, below
 
     # -- alternative models (analysis/alternatives.py) -----------------------
     def lrt_poisson(self, raw, f, cond_of_rep, C):

@@ -114,6 +114,41 @@ class DiagnosticHiC3DeFDR(object):
         out['pixel_dist'] = None if distance is not None else dist
         return out
 
+    def distance_bias_data(self, bins, idx='disp', threshold=0.05):
+        """plot_distance_bias (plotting/distance_bias.py:73-112) for this
+        analysis: ``(bin_labels, p_star, fractions)``. ``bins``: inclusive
+        ``(min, max)`` distance ranges in bin units, either end None for
+        open; ``idx``: 'disp' for the p-values of every disp pixel, 'loop'
+        for those of the loop pixels; ``fractions[b]``: the share of the
+        range's p-values below ``p_star``, the ``100 * threshold``-th
+        percentile of them all (``util.diagnostics.distance_bias``)."""
+        if idx not in ('loop', 'disp'):
+            raise ValueError('idx must be loop or disp')
+        bins = [tuple(b) for b in bins]
+        bin_labels = []
+        for min_dist, max_dist in bins:
+            if min_dist is None and max_dist is not None:
+                label = '<= %s' % max_dist
+            elif min_dist is not None and max_dist is None:
+                label = '>= %s' % min_dist
+            elif min_dist is None and max_dist is None:
+                label = 'all'
+            else:
+                label = '%s to %s' % (min_dist, max_dist)
+            bin_labels.append(label)
+        disp_idx, _ = self.load_data('disp_idx', 'all')
+        if idx == 'loop':
+            loop_idx, _ = self.load_data('loop_idx', 'all')
+            rc_idx, p_idx = (disp_idx, loop_idx), loop_idx
+        else:
+            rc_idx, p_idx = disp_idx, None
+        row, _ = self.load_data('row', 'all', idx=rc_idx)
+        col, _ = self.load_data('col', 'all', idx=rc_idx)
+        pvalues, _ = self.load_data('pvalues', 'all', idx=p_idx)
+        p_star, fractions = diag.distance_bias(
+            pvalues, col.astype(np.int64) - row, bins, threshold=threshold)
+        return bin_labels, p_star, fractions
+
     def ddr_data(self, cond):
         """plot_ddr (plotting.py:158-198, plotting/dispersion.py:343-346):
         ``dist_per_bin``, ``disp_per_bin``, and the fitted curve ``ys`` on

@@ -2,8 +2,8 @@
 
 - ``libh3d.so``          the product: C-ABI host code + gfx950 HIP kernels
                           (csrc/h3d_api.hip, h3d_alt.hip, h3d_balance.hip,
-                          h3d_nb.hip, h3d_diag.hip, h3d_calls.cpp, h3d_npz.cpp;
-                          links zlib), loaded
+                          h3d_nb.hip, h3d_diag.hip, h3d_eval.hip, h3d_calls.cpp,
+                          h3d_npz.cpp; links zlib), loaded
                           by hic3defdr_amd._native.
 - ``libh3d_hosttest.so`` the device numerics compiled for the host, used only
                           by CPU unit tests (tests/test_special_host.py).
@@ -42,6 +42,7 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_bh.hip', 'hipcc'), ('h3d_table.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
                ('h3d_nb.hip', 'hipcc'), ('h3d_diag.hip', 'hipcc'),
+               ('h3d_eval.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]
 HEADERS = ['h3d_special.h', 'h3d_model.h', 'h3d_kernels.h', 'h3d_host.h',
            'h3d_prepare.h', 'h3d_errors.h', 'h3d_ctx.h', 'h3d_lrt_group.h', 'h3d_logtab.h']

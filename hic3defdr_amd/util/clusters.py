@@ -285,3 +285,57 @@ def pixel_in(row, col, prow, pcol, mask=None):
     pos, pk = pos[ok], pk[ok]
     out[pos[keys[pos] == pk]] = True
     return out
+
+
+def _set_pixels(clusters_lists):
+    """The pixels of ``pixel_membership``'s ``clusters_lists`` as one (k, 2)
+    int64 array (repeats kept)."""
+    arrs = []
+    for c in clusters_lists:
+        if isinstance(c, np.ndarray):
+            a = c
+        else:
+            pix = [p for cluster in c for p in cluster]
+            a = np.array(pix, dtype=np.int64) if pix else \
+                np.zeros((0, 2), dtype=np.int64)
+        if a.dtype.kind not in 'iu':
+            raise TypeError('cluster pixels must be integers, not %s'
+                            % a.dtype)
+        if a.size:
+            arrs.append(a.reshape(-1, 2).astype(np.int64, copy=False))
+    if not arrs:
+        return np.zeros((0, 2), dtype=np.int64)
+    return np.concatenate(arrs)
+
+
+def pixel_membership_gpu(row, col, clusters_lists, mask=None):
+    """``pixel_membership`` on the GPU (h3d_pixel_membership): the set's
+    64-bit pixel keys are sorted once on the device and every query pixel is
+    found by a binary search, so the queries may come in any order. Returns
+    a bool vector, one entry per pixel (per pixel where ``mask`` is set).
+    There is no CPU fallback; the arguments are checked before a device is
+    touched."""
+    row, col = np.asarray(row), np.asarray(col)
+    for a, what in ((row, 'row'), (col, 'col')):
+        if a.dtype.kind not in 'iu':
+            raise TypeError('%s must be integers, not %s' % (what, a.dtype))
+        if a.ndim != 1:
+            raise ValueError('%s must have 1 dimension' % what)
+    if row.shape != col.shape:
+        raise ValueError('row and col must have one length')
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.dtype != np.bool_ or mask.shape != row.shape:
+            raise ValueError('mask must be a boolean vector of row\'s length')
+        row, col = row[mask], col[mask]
+    if len(row) >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 pixels')
+    if len(row) and (min(row.min(), col.min()) < 0 or
+                     max(row.max(), col.max()) >= 2 ** 31):
+        raise ValueError('row and col must be in [0, 2^31)')
+    pix = _set_pixels(clusters_lists)
+    if len(pix) >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 set pixels')
+    if len(row) == 0 or len(pix) == 0:
+        return np.zeros(len(row), dtype=bool)
+    return _native.context().pixel_membership(row, col, pix[:, 0], pix[:, 1])

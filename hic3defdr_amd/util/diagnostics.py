@@ -15,7 +15,9 @@ handing them to the reference's own plotters.
 - ``correlation_matrix(data, correlation)``: scipy.stats.spearmanr / pearsonr
   over the replicate pairs (analysis/plotting.py:369-376);
 - ``mvr_data(scaled_cond, dist, disp_fit, disp_per_dist)``: the per-pixel and
-  per-distance quantities of plotting/dispersion.py:133-183.
+  per-distance quantities of plotting/dispersion.py:133-183;
+- ``distance_bias(pvalues, dist, bins, threshold)``: the percentile and the
+  per-range shares of plotting/distance_bias.py:101-112 (csrc/h3d_eval.hip).
 
 Every floating-point sum has a fixed order: a rerun gives the same bits.
 There is no CPU fallback: without libh3d.so or a gfx950 device the functions
@@ -321,3 +323,81 @@ def mvr_data(scaled_cond, dist, disp_fit, disp_per_dist=None, distance=None):
         out['mean_per_bin'] = np.interp(out['dist_per_bin'],
                                         out['dist_range'], out['dist_mean'])
     return out
+
+
+MAX_RANGES = 64     # distance ranges of one distance_bias call
+
+
+def percentile_ranks(n, threshold):
+    """The two 0-based ranks ``np.percentile(x, 100 * threshold)`` (method
+    'linear') reads from the sorted ``x`` of length ``n``, and its weight:
+    ``(previous, next, gamma)``. numpy's own steps: the virtual index
+    ``(n - 1) * (100 * threshold / 100)``, its floor and the rank behind it,
+    both the last rank at or beyond the end."""
+    q = np.true_divide(100 * threshold, 100)
+    vi = (n - 1) * q
+    prev = np.floor(vi)
+    nxt = prev + 1
+    if vi >= n - 1:
+        prev = nxt = -1.0
+    if vi < 0:
+        prev = nxt = 0.0
+    gamma = np.float64(vi - prev)
+    return int(prev) % n, int(nxt) % n, gamma
+
+
+def percentile_lerp(a, b, t):
+    """numpy's ``_lerp``: ``a + (b - a) * t``, and ``b - (b - a) * (1 - t)``
+    for ``t >= 0.5``, in float64, one rounding per operation."""
+    a, b, t = np.float64(a), np.float64(b), np.float64(t)
+    with np.errstate(invalid='ignore'):
+        diff = b - a
+        if t >= 0.5:
+            return b - diff * (1 - t)
+        return a + diff * t
+
+
+def _ranges(bins):
+    lo, hi = [], []
+    for pair in bins:
+        mn, mx = pair
+        lo.append(np.iinfo(np.int64).min if mn is None else int(mn))
+        hi.append(np.iinfo(np.int64).max if mx is None else int(mx))
+    if not 1 <= len(lo) <= MAX_RANGES:
+        raise ValueError('between 1 and %d distance ranges, not %d'
+                         % (MAX_RANGES, len(lo)))
+    return np.array(lo, dtype=np.int64), np.array(hi, dtype=np.int64)
+
+
+def distance_bias(pvalues, dist, bins, threshold=0.05):
+    """plotting/distance_bias.py:101-112: ``(p_star, fractions)``.
+    ``p_star = np.percentile(pvalues, 100 * threshold)``; ``fractions[b] =
+    np.mean(pvalues[idx] < p_star)`` over the pixels whose ``dist`` is in
+    the inclusive range ``bins[b] = (min, max)``, either end None for open;
+    the ranges may overlap, an empty one gives NaN. A NaN p-value makes
+    ``p_star`` NaN and every fraction 0, as numpy does. The sort and the
+    counts run on the GPU (h3d_order_stats, h3d_bin_fractions); the
+    percentile is interpolated here from the two order statistics."""
+    pvalues = _floats(pvalues, 1, 'pvalues')
+    dist = np.asarray(dist)
+    if dist.dtype.kind not in 'iu':
+        raise TypeError('dist must be integers, not %s' % dist.dtype)
+    if dist.shape != pvalues.shape:
+        raise ValueError('pvalues and dist must have one length')
+    lo, hi = _ranges(bins)
+    threshold = float(threshold)
+    if not 0 <= threshold <= 1:
+        raise ValueError('threshold must be in [0, 1]')
+    n = len(pvalues)
+    if n >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 pixels')
+    if n == 0:
+        return np.float64(np.nan), np.full(len(lo), np.nan)
+    ctx = _native.context()
+    prev, nxt, gamma = percentile_ranks(n, threshold)
+    (a, b), n_nan = ctx.order_stats(pvalues, [prev, nxt])
+    p_star = np.float64(np.nan) if n_nan else percentile_lerp(a, b, gamma)
+    members, below = ctx.bin_fractions(pvalues, dist, lo, hi, p_star)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        fractions = below / members.astype(np.float64)
+    return p_star, fractions

@@ -702,6 +702,74 @@ int h3d_balance_pixels(h3d_ctx* ctx, const int32_t* row, const int32_t* col,
                        const int64_t* raw, const double* bias, int64_t n,
                        int R, int n_bins, double* balanced);
 
+/* ---- evaluation against simulated truth ---------------------------------- */
+
+/* Every output below is an integer count or the correctly rounded quotient
+ * of two counts: the results equal the host code's bit for bit, whatever the
+ * launch grid. No floating-point atomics. n < 2^31 throughout. */
+
+/* out (n) bytes: 1 where the query pixel (row[i], col[i]) is in the pixel set
+ * {(prow[j], pcol[j])}, k pixels, repeats allowed -- the Python set lookup of
+ * analysis.py:117-125 and evaluation.py:38-41. The set's keys row << 32 | col
+ * are radix-sorted once on the device, then one binary search per query; the
+ * queries may come in any order. A set pixel with a coordinate outside
+ * [0, 2^31) is dropped (it can match nothing); a query pixel outside that
+ * range is H3D_EARG. k = 0 or n = 0: zeros, no launch. _dev: every array is
+ * a device pointer; synchronous. */
+int h3d_pixel_membership(h3d_ctx* ctx, const int64_t* row, const int64_t* col,
+                         int64_t n, const int64_t* prow, const int64_t* pcol,
+                         int64_t k, uint8_t* out);
+int h3d_pixel_membership_dev(h3d_ctx* ctx, const int64_t* d_row,
+                             const int64_t* d_col, int64_t n,
+                             const int64_t* d_prow, const int64_t* d_pcol,
+                             int64_t k, uint8_t* d_out);
+
+/* evaluation.py:73-78: scikit-learn's _binary_clf_curve and roc_curve on
+ * labels (n) bytes (non-zero = positive) and scores (n), plus the FDR points,
+ * from one radix sort of (score, label). complement != 0: the score is
+ * 1 - scores[i], formed on the device (evaluate() passes q-values). Per run
+ * of equal scores (-0.0 and +0.0 one value), descending: tps = the positives
+ * so far, fps = the rest, thresh = the score; with drop_intermediate and more
+ * than two runs, only the first, the last and those where the second
+ * difference of fps or of tps is non-zero; then the origin (0, 0,
+ * thresh[1] + 1) in front (scikit-learn 0.24's opening). fpr = fps /
+ * fps[m - 1], tpr = tps / tps[m - 1] (0 / 0 = NaN, as the host's); fdr[i] =
+ * fps[i] / (fps[i] + tps[i]) at i = start, start + rate, ..., NaN elsewhere,
+ * rate = max(m / n_fdr_points, 1), start = the first i with tps[i] > 0 (0
+ * without one). The six outputs have room for n + 1 entries; *m_out = the
+ * number of points m written to each. *flags: H3D_FLAG_BADIN when a score is
+ * NaN (scikit-learn raises; the outputs are then meaningless). n >= 1,
+ * n_fdr_points >= 1. _dev: labels, scores and the six outputs are device
+ * pointers; synchronous. */
+int h3d_roc_curve(h3d_ctx* ctx, const uint8_t* labels, const double* scores,
+                  int64_t n, int64_t n_fdr_points, int drop_intermediate,
+                  int complement, double* fdr, double* fpr, double* tpr,
+                  double* thresh, int64_t* fps, int64_t* tps, int64_t* m_out,
+                  int* flags);
+int h3d_roc_curve_dev(h3d_ctx* ctx, const uint8_t* d_labels,
+                      const double* d_scores, int64_t n, int64_t n_fdr_points,
+                      int drop_intermediate, int complement, double* d_fdr,
+                      double* d_fpr, double* d_tpr, double* d_thresh,
+                      int64_t* d_fps, int64_t* d_tps, int64_t* m_out,
+                      int* flags);
+
+/* out[j] = the value at rank ranks[j] (0-based, in [0, n)) of values (n)
+ * sorted ascending with every NaN last, K <= 64 ranks; *nan_count = the NaNs.
+ * The order statistics np.percentile interpolates between
+ * (plotting/distance_bias.py:103); the interpolation itself stays on the
+ * host. Host buffers. */
+int h3d_order_stats(h3d_ctx* ctx, const double* values, int64_t n,
+                    const int64_t* ranks, int K, double* out,
+                    int64_t* nan_count);
+
+/* plotting/distance_bias.py:106-112 for B <= 64 inclusive distance ranges
+ * [lo[b], hi[b]] (they may overlap; an open end is INT64_MIN / INT64_MAX):
+ * members[b] = the pixels with dist in the range, below[b] = those of them
+ * with p < p_star (a NaN p or p_star counts as not below). Host buffers. */
+int h3d_bin_fractions(h3d_ctx* ctx, const double* p, const int64_t* dist,
+                      int64_t n, const int64_t* lo, const int64_t* hi, int B,
+                      double p_star, int64_t* members, int64_t* below);
+
 /* ---- measurement -------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on the ctx stream; on = 0 off, 1 the roofline
