@@ -362,8 +362,10 @@ static __global__ void k_minus_one(int32_t* __restrict__ v, int64_t n) {
 // in its order (analysis.py:174-183 and :272-275, numpy evaluates left to
 // right; a product of three never contracts, so the bits are numpy's). sel
 // = the selected union-pixel indices (DeviceSelect over disp_idx). sf is
-// (N, R), or (R,) with sf_per_rep (the non-conditional norms). Rows of R <= 4
-// int32 / f64 go out as whole 16 B words where aligned.
+// (N, R), or (R,) with sf_per_rep (the non-conditional norms). One lane per
+// output pixel writes its R counts and R products element by element. row and
+// col index bias unchecked: they are the caller's union of the chromosome's
+// own bins.
 static __global__ void k_disp_pixels(const int32_t* __restrict__ sel, int64_t n_out,
                                      const int32_t* __restrict__ row,
                                      const int32_t* __restrict__ col,

@@ -273,24 +273,34 @@ def exchange_compact(ctx, t_raw, t_dist, keys, owner, group=None, chunks=1):
     -- then f by h3d_pixel_f_dev from the
     stacked bias / size-factor tables (PixelKeys.device_tables). Returns the
     received (raw (m, R) int32, f (m, R) float64, dist (m,) int32), bit for
-    bit what exchange_by_owner delivers."""
+    bit what exchange_by_owner delivers. An input only one rank can see is
+    wrong -- a negative value (ValueError), a key outside the tables
+    (H3DError from h3d_pixel_f_dev) -- raises on every rank together: the
+    first rides in the all-reduce of the maxima, the second is agreed on by
+    one 1-element all-reduce after f."""
     import torch
     import torch.distributed as dist
+    from hic3defdr_amd import _native
     dev = t_raw.device
     xdev = _xdev(dev, group)
     n, R = t_raw.shape
     tabs = keys.device_tables(dev, R, group)
-    mx = torch.zeros(4, dtype=torch.int64, device=dev)
+    # the four maxima and, as a fifth, minus the least value: one rank's
+    # negative count, distance or key is every rank's error (a rank that
+    # raised alone would leave the others waiting in the exchange)
+    mx = torch.zeros(5, dtype=torch.int64, device=dev)
     if n:
+        lo = torch.stack([t_raw.min().long(), t_dist.min().long(),
+                          keys.chrom.min().long(), keys.sfi.min().long()])
         mx = torch.stack([t_raw.max().long(), t_dist.max().long(),
-                          keys.chrom.max().long(), keys.sfi.max().long()])
-    lo = min(int(t_raw.min()), int(t_dist.min()), int(keys.chrom.min()),
-             int(keys.sfi.min())) if n else 0
-    if lo < 0:
-        raise ValueError('exchange_compact: negative count, distance or key')
+                          keys.chrom.max().long(), keys.sfi.max().long(),
+                          -lo.min()])
     mx = mx.to(xdev)
     dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
-    w = [_narrowest(int(v)) for v in mx.tolist()]
+    mx = mx.tolist()
+    if mx[4] > 0:
+        raise ValueError('exchange_compact: negative count, distance or key')
+    w = [_narrowest(int(v)) for v in mx[:4]]
     cols = [t_raw.to(w[0]), keys.row.to(torch.int32), t_dist.to(w[1]),
             keys.chrom.to(w[2]), keys.sfi.to(w[3])]
     raw_m, row_m, dist_m, chrom_m, sfi_m = exchange_columns(cols, owner,
@@ -299,15 +309,29 @@ def exchange_compact(ctx, t_raw, t_dist, keys, owner, group=None, chunks=1):
     raw_m = raw_m.to(torch.int32)
     dist_m = dist_m.to(torch.int32).contiguous()
     f_m = torch.empty((m, R), dtype=torch.float64, device=dev)
+    err = None
     if m:
         row_m = row_m.contiguous()
         chrom_m = chrom_m.to(torch.int32).contiguous()
         sfi_m = sfi_m.to(torch.int32).contiguous()
-        ctx.pixel_f_dev(row_m.data_ptr(), dist_m.data_ptr(),
-                        chrom_m.data_ptr(), sfi_m.data_ptr(), m, R,
-                        tabs[0].data_ptr(), tabs[1].data_ptr(),
-                        tabs[2].data_ptr(), tabs[3].data_ptr(), keys.nchrom,
-                        f_m.data_ptr())
+        try:
+            ctx.pixel_f_dev(row_m.data_ptr(), dist_m.data_ptr(),
+                            chrom_m.data_ptr(), sfi_m.data_ptr(), m, R,
+                            tabs[0].data_ptr(), tabs[1].data_ptr(),
+                            tabs[2].data_ptr(), tabs[3].data_ptr(),
+                            keys.nchrom, f_m.data_ptr())
+        except _native.H3DError as e:
+            err = e
+    # a key outside the tables on one rank is every rank's error (the ranks
+    # without pixels included): the others would wait in the next collective
+    bad = torch.tensor([int(err is not None)], dtype=torch.int64, device=xdev)
+    dist.all_reduce(bad, op=dist.ReduceOp.MAX, group=group)
+    if err is not None:
+        raise err
+    if int(bad.item()):
+        raise _native.H3DError(
+            'exchange_compact: h3d_pixel_f_dev failed on another rank',
+            code=-5)
     return raw_m.contiguous(), f_m, dist_m
 
 

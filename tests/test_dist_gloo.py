@@ -547,3 +547,71 @@ def test_compact_reshard_equals_full_record(world):
     assert parallel.compact_record_bytes(4, 30000, 250, 20, 40) == 15
     assert parallel.compact_record_bytes(4, 1 << 20, 250, 20, 40) == 23
     assert parallel.compact_record_bytes(4, 30000, 400, 300, 40) == 17
+
+
+class _FailingCtx(_HostCtx):
+    """_HostCtx whose pixel_f_dev fails as libh3d does for a key outside
+    the tables (H3DError, code -5)."""
+
+    def pixel_f_dev(self, *args):
+        from hic3defdr_amd import _native
+        raise _native.H3DError('pixel keys outside the bias / size-factor '
+                               'tables', code=-5)
+
+
+def _compact_error_worker(rank, world, port, mode, result_file):
+    """exchange_compact where rank 1 alone has the bad input: a negative
+    size-factor row ('negative'), or a pixel_f_dev that fails ('pixel_f').
+    The last rank of world 3 holds no pixel and owns none (m == 0). Every
+    rank writes what it raised; a rank left waiting in a collective gives up
+    after the group's 30 s and writes that error instead."""
+    import datetime
+    import torch
+    import torch.distributed as dist
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world,
+                            timeout=datetime.timedelta(seconds=30))
+    rng = np.random.default_rng(40 + rank)
+    R, nb, S = 4, 50, 3
+    n = 0 if rank == 2 else 300
+    raw = torch.from_numpy(rng.integers(0, 500, (n, R)).astype(np.int32))
+    d = rng.integers(0, 12, n).astype(np.int32)
+    sfi = rng.integers(0, S, n).astype(np.int32)
+    if mode == 'negative' and rank == 1:
+        sfi[n // 2] = -1
+    tables = {rank: (np.exp(rng.normal(0, 0.2, (nb, R))),
+                     rng.uniform(0.5, 2.0, (S, R)))} if n else {}
+    keys = parallel.PixelKeys(
+        torch.from_numpy(rng.integers(0, nb - 12, n).astype(np.int32)),
+        torch.full((n,), rank, dtype=torch.int32), torch.from_numpy(sfi),
+        tables, 2)
+    owner = torch.from_numpy((d % 2).astype(np.int64))
+    ctx = _FailingCtx() if mode == 'pixel_f' and rank == 1 else _HostCtx()
+    what = 'returned'
+    try:
+        parallel.exchange_compact(ctx, raw, torch.from_numpy(d), keys, owner,
+                                  chunks=3)
+    except Exception as e:   # noqa: BLE001 -- the test names the type
+        what = '%s code=%s' % (type(e).__name__, getattr(e, 'code', None))
+    with open(result_file % rank, 'w') as fh:
+        fh.write(what)
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize('world', [2, 3])
+@pytest.mark.parametrize('mode,want', [('negative', 'ValueError code=None'),
+                                       ('pixel_f', 'H3DError code=-5')])
+def test_compact_reshard_fails_on_every_rank_together(mode, want, world):
+    """An input of exchange_compact that only one rank can see is wrong -- a
+    negative key before the exchange, a key h3d_pixel_f_dev rejects after it
+    -- raises the same error on every rank (the rank without pixels
+    included), so that no rank is left waiting in a collective."""
+    with tempfile.TemporaryDirectory() as tmp:
+        res = os.path.join(tmp, 'e_%d.txt')
+        port = 29400 + (os.getpid() % 1000) + world + \
+            (20 if mode == 'pixel_f' else 0)
+        mp.spawn(_compact_error_worker, args=(world, port, mode, res),
+                 nprocs=world, join=True)
+        got = [open(res % r).read() for r in range(world)]
+    assert got == [want] * world, got

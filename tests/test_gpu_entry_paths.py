@@ -6,6 +6,8 @@ that are only known after a device round trip, and the BH temp buffer shared
 by three hipcub operations. Every expectation is the library's behaviour
 (checked against the CPU oracle where there is one); the growth cases use a
 context of their own, since the suite's shared one has grown its buffers."""
+import warnings
+
 import numpy as np
 import pytest
 import scipy.sparse as sparse
@@ -75,6 +77,84 @@ def test_size_factors_host_and_device_entry(ctx, norm, n_bins, R):
     else:
         np.testing.assert_array_equal(host, got)
     np.testing.assert_array_equal(t_sf.cpu().numpy(), got)
+
+
+# The conditional norms where the shapes above never go: bins much smaller
+# than a wave (k_mor_keys counts a bin's valid rows by ballots over the
+# wave's bins), a bin without an all-positive row (the median of nothing is
+# NaN, and the interpolation carries it to the neighbouring bins' pixels),
+# more bins than pixels, one replicate, and a second, partly filled
+# grid-stride trip. name: (seed, n, R, n_bins, distances below, emptied).
+SF_EDGES = {
+    'many bins per wave': (1, 130, 3, 40, 60, False),
+    'bin without a valid row': (2, 257, 9, 7, 40, True),
+    'distance without a valid row': (4, 193, 8, 0, 40, True),
+    'more bins than pixels': (3, 5, 3, 7, 40, False),
+    'one replicate, bins': (5, 300, 1, 7, 40, False),
+    'one replicate, distances': (6, 300, 1, 0, 40, False),
+    'second grid-stride trip': (7, None, 2, 20, 200, False),
+}
+
+
+def _sf_edge_inputs(name, n_full):
+    """(bal, dist, n_bins, emptied pixels or None) of an SF_EDGES case,
+    drawn as _sf_inputs draws; ``n_full`` stands in for n = None."""
+    seed, n, R, n_bins, dmax, emptied = SF_EDGES[name]
+    rng = np.random.default_rng(seed)
+    n = n or n_full
+    if n_bins > n:      # distinct distances: no two bins share their mean
+        dist = rng.permutation(dmax)[:n].astype(np.int32)
+    else:
+        dist = rng.integers(0, dmax, n).astype(np.int32)
+    bal = np.exp(rng.normal(1, 1, (n, R))) * (rng.random((n, R)) > 0.05)
+    gone = None
+    if emptied:     # replicate 0 zeroed throughout one bin / one distance
+        gone = oracle.equal_bin(dist, n_bins) == 3 if n_bins else dist == 17
+        assert gone.any()
+        bal[gone, 0] = 0.0
+    return bal, dist, n_bins, gone
+
+
+def _sf_edge_check(name, norm, got, ref, gone):
+    """The NaN masks agree, the finite factors within the project's bound
+    for size factors, and the case does what its name says."""
+    assert got.shape == ref.shape
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(ref))
+    fin = np.isfinite(ref)
+    err = rel_err(got[fin], ref[fin])
+    frac = float(np.isnan(ref).mean())
+    print('%s %s: rel_err %.3g over %d finite, %.1f %% NaN'
+          % (name, norm, err, int(fin.sum()), 100 * frac))
+    assert fin.sum() == (~np.isnan(ref)).sum()      # no infinite factor
+    assert err < 1e-13
+    if norm == 'conditional_mor':
+        assert frac <= 1.0 / 3
+        if gone is not None:
+            assert np.isnan(ref[gone]).all()
+    else:
+        assert frac == 0.0
+
+
+@pytest.mark.parametrize('norm', ['conditional_mor', 'conditional_scaling'])
+@pytest.mark.parametrize('name', sorted(SF_EDGES))
+def test_size_factors_edges(ctx, name, norm):
+    import torch
+    n_full = torch.cuda.get_device_properties(0).multi_processor_count * \
+        8 * 256 + 37    # one more trip than grid_for's widest grid covers
+    bal, dist, n_bins, gone = _sf_edge_inputs(name, n_full)
+    n, R = bal.shape
+    with np.errstate(all='ignore'), warnings.catch_warnings():
+        warnings.simplefilter('ignore')     # numpy's median of nothing
+        ref = getattr(oracle, norm)(bal, dist, n_bins=n_bins or None)
+    got = ctx.size_factors(bal, dist, norm, n_bins)
+    _sf_edge_check(name, norm, got, ref, gone)
+    t_bal = _dev(bal)
+    t_sf = torch.empty((n, R), dtype=torch.float64, device='cuda:0')
+    torch.cuda.synchronize()
+    assert ctx.size_factors_dev(t_bal.data_ptr(), dist, n, R, norm, n_bins,
+                                d_sf_out=t_sf.data_ptr(),
+                                host_out=False) is None
+    _sf_edge_check(name, norm, t_sf.cpu().numpy(), ref, gone)
 
 
 @pytest.mark.parametrize('R', [3, 6])

@@ -119,6 +119,36 @@ def test_two_ranks_run_to_qvalues_matches_reference(name, shard, backend):
         shutil.rmtree(outdir, ignore_errors=True)
 
 
+def test_two_ranks_compact_reshard_equals_full_record():
+    """The distance re-shard's compact exchange on the GPU, 2 ranks on
+    cuda:0 over gloo (tests/dist_keys_main.py): Resident.disp_keys' keys and
+    tables, PixelKeys.device_tables across the ranks and h3d_pixel_f_dev
+    deliver raw, f and dist as the full record does, in dtype, shape and
+    every bit -- per-pixel and per-replicate size factors, R = 4 and 9, a
+    chromosome without disp pixels, the exchange in 1 and 3 parts."""
+    env = dict(os.environ, H3D_DEVICE='0', MASTER_ADDR='127.0.0.1',
+               OMP_NUM_THREADS='1')
+    port = 29680 + os.getpid() % 1000
+    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
+           '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
+           '--master-port', str(port),
+           os.path.join(REPO, 'tests', 'dist_keys_main.py')]
+    with tempfile.TemporaryDirectory() as tmp:
+        log = os.path.join(tmp, 'ranks.log')
+        with open(log, 'w') as fh:
+            try:
+                rc = subprocess.run(cmd, env=env, stdout=fh,
+                                    stderr=subprocess.STDOUT,
+                                    timeout=150).returncode
+            except subprocess.TimeoutExpired:
+                rc = 'timeout'
+        text = open(log).read()
+    assert rc == 0, text[-4000:]
+    for rank in range(2):
+        assert re.search(r'rank %d of 2: \d+ variants, \d+ pixels received, '
+                         r'bit-identical=True' % rank, text), text[-4000:]
+
+
 def test_bh_sharded_gpu():
     """parallel.bh_sharded on the GPU (DeviceBhOps) with 3 ranks on cuda:0
     over gloo, 3 M p-values with ties, NaN and a heavy tie at 1: every q
