@@ -1,10 +1,8 @@
 """In-tree build of the native libraries (no cmake; plain hipcc / g++).
 
 - ``libh3d.so``          the product: C-ABI host code + gfx950 HIP kernels
-                          (csrc/h3d_api.hip, h3d_alt.hip, h3d_balance.hip,
-                          h3d_nb.hip, h3d_diag.hip, h3d_eval.hip, h3d_calls.cpp,
-                          h3d_npz.cpp; links zlib), loaded
-                          by hic3defdr_amd._native.
+                          (the units of ``NATIVE_SRCS`` below; links zlib),
+                          loaded by hic3defdr_amd._native.
 - ``libh3d_hosttest.so`` the device numerics compiled for the host, used only
                           by CPU unit tests (tests/test_special_host.py).
 - ``libh3d_selftest.so`` the same numerics compiled for gfx950 behind the same
@@ -18,7 +16,9 @@ repo snapshot (they are git-ignored, not gpurun-ignored).
 
 Staleness is decided by CONTENT, not mtimes: every output carries a
 ``.stamp`` file holding the sha256 of its compile command and of every source
-and header it is built from, and is rebuilt whenever that digest changes. A
+and header it is built from, and is rebuilt whenever that digest changes. The
+headers are every ``csrc/*.h`` plus ``include/h3d.h``, listed from the
+directory, so a new header cannot be left out of the digests. A
 binary copied from another tree (or a stale one whose sources were edited
 with an older mtime) is therefore never silently reused.
 """
@@ -42,10 +42,8 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_bh.hip', 'hipcc'), ('h3d_table.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
                ('h3d_nb.hip', 'hipcc'), ('h3d_diag.hip', 'hipcc'),
-               ('h3d_eval.hip', 'hipcc'),
+               ('h3d_eval.hip', 'hipcc'), ('h3d_ctx.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]
-HEADERS = ['h3d_special.h', 'h3d_model.h', 'h3d_kernels.h', 'h3d_host.h',
-           'h3d_prepare.h', 'h3d_errors.h', 'h3d_ctx.h', 'h3d_lrt_group.h', 'h3d_logtab.h']
 # concurrent compiles (each hipcc TU is single-threaded; the box sets
 # MAX_JOBS=16, this container has 8 CPUs)
 JOBS = max(1, min(int(os.environ.get('MAX_JOBS', '8')), os.cpu_count() or 1))
@@ -90,8 +88,8 @@ def _build(target, cmd, deps, force):
 
 
 def _headers():
-    return [os.path.join(CSRC, h) for h in HEADERS] + \
-        [os.path.join(INC, 'h3d.h')]
+    return sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC)
+                  if h.endswith('.h')) + [os.path.join(INC, 'h3d.h')]
 
 
 def build_hosttest(force=False):

@@ -223,28 +223,19 @@ int h3d_lrt_poisson(h3d_ctx* ctx, const int64_t* raw, const double* f,
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (n == 0) return 0;
   if (!raw || !f || !p || !llr || !mu0 || !mu1) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_f = sc.get<double>("in_f", n * R);
-  double* d_out = sc.get<double>("plrt_out", n * (3 + C));
-  if (!sc.ok) return fail(H3D_ENOMEM, "poisson inputs");
-  int32_t* d_raw = nullptr;
-  int* d_ovf = nullptr;
-  if (int rc = upload_counts(ctx, raw, n * R, &d_raw, &d_ovf)) return rc;
-  HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  int32_t* d_raw = hc.counts(raw, n * R, "raw counts must be in [0, 2^31)");
+  double* d_f = hc.in("in_f", f, n * R);
+  double* d_out = hc.out<double>("plrt_out", n * (3 + C));  // p | llr | mu0 | mu1
+  if (int rc = hc.ready("poisson inputs")) return rc;
   double *dp = d_out, *dl = d_out + n, *dm0 = d_out + 2 * n, *dm1 = d_out + 3 * n;
-  int rc = h3d_lrt_poisson_dev(ctx, d_raw, d_f, n, R, C, cond_of_rep, dp, dl, dm0, dm1);
-  if (rc) return rc;
-  int ovf = 0;
-  if (int orc = counts_ovf_copy(ctx, d_ovf, &ovf)) return orc;
-  HIP_TRY(hipMemcpyAsync(p, dp, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(llr, dl, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(mu0, dm0, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(mu1, dm1, n * C * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (ovf) return fail(H3D_EINPUT, "raw counts must be in [0, 2^31)");
-  return 0;
+  if (int rc = h3d_lrt_poisson_dev(ctx, d_raw, d_f, n, R, C, cond_of_rep, dp, dl, dm0, dm1))
+    return rc;
+  hc.back(p, dp, n);
+  hc.back(llr, dl, n);
+  hc.back(mu0, dm0, n);
+  hc.back(mu1, dm1, n * C);
+  return hc.finish();
 }
 
 int h3d_mme_per_pixel(h3d_ctx* ctx, const double* data, const double* f,
@@ -256,17 +247,13 @@ int h3d_mme_per_pixel(h3d_ctx* ctx, const double* data, const double* f,
   if (int rc = check_cond(cond_of_rep, R, C, &nrep, &rep_idx)) return rc;
   if (n == 0) return 0;
   if (!data || !disp) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_data = sc.get<double>("mme_in", n * R);
-  double* d_f = f ? sc.get<double>("mme_f", n * R) : nullptr;
-  double* d_out = sc.get<double>("mme_out", n * C);
-  int32_t* d_cond = sc.get<int32_t>("cond_of_rep", R);
-  if (!sc.ok) return fail(H3D_ENOMEM, "mme scratch");
-  HIP_TRY(hipMemcpyAsync(d_data, data, n * R * 8, hipMemcpyHostToDevice, s));
-  if (f) HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_cond, cond_of_rep, R * 4, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_data = hc.in("mme_in", data, n * R);
+  double* d_f = hc.in("mme_f", f, n * R);
+  double* d_out = hc.out<double>("mme_out", n * C);
+  int32_t* d_cond = hc.in("cond_of_rep", cond_of_rep, R);
+  if (int rc = hc.ready("mme scratch")) return rc;
   const int grid = alt_grid(ctx, n);
   {
     ProfScope ps(ctx, "mme", n, 1);
@@ -281,9 +268,8 @@ int h3d_mme_per_pixel(h3d_ctx* ctx, const double* data, const double* f,
                          d_f, n, R, C, d_cond, min_disp, d_out);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(disp, d_out, n * C * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(disp, d_out, n * C);
+  return hc.finish();
 }
 
 }  // extern "C"

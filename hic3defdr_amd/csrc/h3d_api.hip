@@ -28,161 +28,6 @@ using namespace h3d;
 using namespace h3dint;
 using h3derr::fail;
 
-namespace h3dint {
-
-void* scratch(h3d_ctx* ctx, const char* slot, size_t bytes) {
-  auto& b = ctx->bufs[slot];
-  if (b.second >= bytes && b.first) return b.first;
-  if (b.first) (void)hipFree(b.first);
-  b.first = nullptr;
-  b.second = 0;
-  void* p = nullptr;
-  if (hipMalloc(&p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-  b.first = p;
-  b.second = std::max<size_t>(bytes, 256);
-  return p;
-}
-
-void* scratch_keep(h3d_ctx* ctx, const char* slot, size_t bytes, size_t keep) {
-  auto& b = ctx->bufs[slot];
-  if (b.first && b.second >= bytes) return b.first;
-  const size_t cap = std::max<size_t>(std::max(bytes, 2 * b.second), 256);
-  void* p = nullptr;
-  if (hipMalloc(&p, cap) != hipSuccess) return nullptr;
-  if (b.first) {
-    if (keep) (void)hipMemcpyAsync(p, b.first, std::min(keep, b.second),
-                                   hipMemcpyDeviceToDevice, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(b.first);
-  }
-  b.first = p;
-  b.second = cap;
-  return p;
-}
-
-int h2d_pinned(h3d_ctx* ctx, void* d_dst, const void* src, size_t bytes, hipStream_t s) {
-  if (bytes == 0) return 0;
-  const size_t need = (bytes + 255) & ~(size_t)255;
-  if (!ctx->bounce_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->bounce_ev, hipEventDisableTiming));
-  // the buffer is rewritten only after every earlier copy out of it has
-  // read it: wrap-around, growth and a change of stream wait on the last one
-  const bool wrap = ctx->bounce_off + need > ctx->bounce.cap;
-  if ((wrap || (ctx->bounce_stream && ctx->bounce_stream != s)) && ctx->bounce_stream) {
-    HIP_TRY(hipEventSynchronize(ctx->bounce_ev));
-    ctx->bounce_off = 0;
-    ctx->bounce_stream = nullptr;
-  }
-  if (need > ctx->bounce.cap) {
-    if (int rc = ctx->bounce.grow(need, (size_t)1 << 20)) return rc;
-    ctx->bounce_off = 0;
-  }
-  char* b = (char*)ctx->bounce.p + ctx->bounce_off;
-  std::memcpy(b, src, bytes);
-  HIP_TRY(hipMemcpyAsync(d_dst, b, bytes, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(ctx->bounce_ev, s));
-  ctx->bounce_stream = s;
-  ctx->bounce_off += need;
-  return 0;
-}
-
-void* pinned_rd(h3d_ctx* ctx, size_t bytes) {
-  return ctx->land.grow(bytes, 4096) ? nullptr : ctx->land.p;
-}
-
-int counts_to_i32(h3d_ctx* ctx, const int64_t* d_raw64, int32_t* d_raw, int64_t count,
-                  int* d_ovf) {
-  HIP_TRY(hipMemsetAsync(d_ovf, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(k_i64_to_i32, dim3(grid_for(ctx, count)), dim3(kBlock), 0, ctx->stream,
-                     d_raw64, d_raw, count, d_ovf);
-  return 0;
-}
-
-int upload_counts(h3d_ctx* ctx, const int64_t* raw64, int64_t count, int32_t** d_raw,
-                  int** d_ovf) {
-  Scratch sc{ctx};
-  int64_t* d_raw64 = sc.get<int64_t>("in_raw64", count);
-  *d_raw = sc.get<int32_t>("in_raw", count);
-  *d_ovf = sc.get<int>("ovf", 1);
-  if (!sc.ok) return fail(H3D_ENOMEM, "raw counts");
-  HIP_TRY(hipMemcpyAsync(d_raw64, raw64, count * 8, hipMemcpyHostToDevice, ctx->stream));
-  return counts_to_i32(ctx, d_raw64, *d_raw, count, *d_ovf);
-}
-
-int counts_ovf_copy(h3d_ctx* ctx, const int* d_ovf, int* h_ovf) {
-  HIP_TRY(hipMemcpyAsync(h_ovf, d_ovf, 4, hipMemcpyDeviceToHost, ctx->stream));
-  return 0;
-}
-
-int d2h_sync(h3d_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t s) {
-  void* l = pinned_rd(ctx, bytes);
-  if (!l) return fail(H3D_ENOMEM, "pinned landing zone");
-  HIP_TRY(hipMemcpyAsync(l, d_src, bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(dst, l, bytes);
-  return 0;
-}
-
-hipEvent_t ev_get(h3d_ctx* ctx) {
-  if (!ctx->event_pool.empty()) {
-    hipEvent_t e = ctx->event_pool.back();
-    ctx->event_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
-void prof_collect(h3d_ctx* ctx) {
-  if (ctx->pending.empty()) return;
-  (void)hipStreamSynchronize(ctx->stream);
-  for (size_t i = 0; i < ctx->pending.size(); ++i) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ctx->pending[i].second.first,
-                              ctx->pending[i].second.second);
-    auto& e = ctx->stats[ctx->pending[i].first];
-    e.ms += ms;
-    e.launches += 1;
-    e.units += ctx->pending_units[i];
-    ctx->event_pool.push_back(ctx->pending[i].second.first);
-    ctx->event_pool.push_back(ctx->pending[i].second.second);
-  }
-  ctx->pending.clear();
-  ctx->pending_units.clear();
-}
-
-int grid_for(h3d_ctx* ctx, int64_t n, int per_cu) {
-  int64_t g = (n + kBlock - 1) / kBlock;
-  g = std::min<int64_t>(g, (int64_t)ctx->n_cu * per_cu);
-  return (int)std::max<int64_t>(g, 1);
-}
-
-int check_cond(const int32_t* cond_of_rep, int R, int C, std::vector<int>* nrep,
-               std::vector<int32_t>* rep_idx) {
-  if (R < 1 || R > kMaxReps) return fail(H3D_EARG, "R=%d outside [1, %d]", R, kMaxReps);
-  if (C < 1 || C > kMaxConds) return fail(H3D_EARG, "C=%d outside [1, %d]", C, kMaxConds);
-  nrep->assign(C, 0);
-  rep_idx->assign((size_t)C * kMaxReps, 0);
-  for (int r = 0; r < R; ++r) {
-    const int c = cond_of_rep[r];
-    if (c < 0 || c >= C) return fail(H3D_EARG, "cond_of_rep[%d]=%d", r, c);
-    (*rep_idx)[(size_t)c * kMaxReps + (*nrep)[c]] = r;
-    (*nrep)[c] += 1;
-  }
-  for (int c = 0; c < C; ++c)
-    if ((*nrep)[c] == 0) return fail(H3D_EARG, "condition %d has no replicates", c);
-  return 0;
-}
-
-int flags_to_code(int fl) {
-  if (fl & kFlagBadInput) return fail(H3D_EINPUT, "non-positive or non-finite dispersion / scaling factor (status %d)", fl);
-  if (fl & (kFlagNoRoot | kFlagNoConv)) return fail(H3D_ENOCONV, "mean MLE failed (status %d)", fl);
-  if (fl & (kFlagBrentFail | kFlagQcmlGuard)) return fail(H3D_ENOCONV, "dispersion optimisation failed (status %d)", fl);
-  return 0;
-}
-
-}  // namespace h3dint
-
 namespace {
 
 // H3D_TIMING=1: host-side stage stamps of the estimate_disp driver (stderr)
@@ -1421,23 +1266,16 @@ int h3d_disp_per_dist(h3d_ctx* ctx, const int64_t* raw, const double* f,
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (n > 0 && (!raw || !f || !dist)) return fail(H3D_EARG, "null input");
   HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
   int32_t* d_raw = nullptr;
   double* d_f = nullptr;
   int32_t* d_dist = nullptr;
-  if (n > 0) {
-    Scratch sc{ctx};
-    d_f = sc.get<double>("in_f", n * R);
-    d_dist = sc.get<int32_t>("in_dist", n);
-    if (!sc.ok) return fail(H3D_ENOMEM, "inputs");
-    int* d_ovf = nullptr;
-    if (int rc = upload_counts(ctx, raw, n * R, &d_raw, &d_ovf)) return rc;
-    HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_dist, dist, n * 4, hipMemcpyHostToDevice, s));
-    int ovf = 0;
-    if (int rc = counts_ovf_copy(ctx, d_ovf, &ovf)) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ovf) return fail(H3D_EINPUT, "raw counts must be in [0, 2^31)");
+  if (n > 0) {  // the counts are checked before the driver starts
+    HostCall hc(ctx);
+    d_raw = hc.counts(raw, n * R, "raw counts must be in [0, 2^31)");
+    d_f = hc.in("in_f", f, n * R);
+    d_dist = hc.in("in_dist", dist, n);
+    if (int rc = hc.ready("inputs")) return rc;
+    if (int rc = hc.finish()) return rc;
   }
   return h3d_disp_per_dist_dev(ctx, d_raw, d_f, d_dist, n, R, C, cond_of_rep, D,
                                estimator, disp_per_dist, seg_flags, nullptr, nullptr);
@@ -1529,29 +1367,24 @@ int h3d_cml(h3d_ctx* ctx, const double* data, int64_t n, int r, double* disp_out
   for (int k = 0; k < kMaxReps; ++k) rep_idx[k] = k;
   const int64_t seg[2] = {0, n};
   const int32_t nrep = r;
-  Scratch sc{ctx};
-  double* d_pd = sc.get<double>("cml_pd", (size_t)n * r);
-  int64_t* d_seg = sc.get<int64_t>("cml_seg", 2);
-  int32_t* d_ri = sc.get<int32_t>("cml_ri", kMaxReps);
-  int32_t* d_nr = sc.get<int32_t>("cml_nr", 1);
-  SegState* d_st = sc.get<SegState>("cml_st", 1);
-  int* d_fl = sc.get<int>("cml_fl", 1);
-  double* d_res = sc.get<double>("cml_res", 1);
-  int* d_q = sc.get<int>("cml_queue", 1);
-  if (!sc.ok) return fail(H3D_ENOMEM, "cml scratch");
-  HIP_TRY(hipMemcpyAsync(d_pd, soa.data(), soa.size() * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_seg, seg, 16, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_ri, rep_idx.data(), kMaxReps * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_nr, &nrep, 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_st, &st, sizeof(SegState), hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_pd = hc.in("cml_pd", soa.data(), (size_t)n * r);
+  int64_t* d_seg = hc.in("cml_seg", seg, 2);
+  int32_t* d_ri = hc.in("cml_ri", rep_idx.data(), kMaxReps);
+  int32_t* d_nr = hc.in("cml_nr", &nrep, 1);
+  SegState* d_st = hc.in("cml_st", &st, 1);
+  int* d_fl = hc.out<int>("cml_fl", 1);
+  double* d_res = hc.out<double>("cml_res", 1);
+  int* d_q = hc.out<int>("cml_queue", 1);
+  if (int rc = hc.ready("cml scratch")) return rc;
   HIP_TRY(hipMemsetAsync(d_fl, 0, 4, s));
   with_width(r <= 4 ? 4 : r <= 8 ? 8 : r <= 16 ? 16 : 32, false, [&](auto m, auto) {
     launch_brent<decltype(m)::value>(ctx, d_pd, n, d_seg, 1, 1, d_ri, d_nr, d_st, d_fl, d_res,
                                      d_q);
   });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof(SegState), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  hc.back(&st, d_st, 1);
+  if (int rc = hc.finish()) return rc;
   if (st.flags & kFlagBrentFail)
     return fail(H3D_ENOCONV, "bounded minimisation failed (reference: assert res.success)");
   // the search ended in seg_step's qcml update: disp = delta / (1 - delta)

@@ -556,7 +556,7 @@ int check_csr(const void* ctx, const int64_t* indptr, const int32_t* indices, co
 
 // the device copy of the matrix and what the set-up stage derives from it
 struct Setup {
-  h3d_ctx* ctx;
+  HostCall& hc;
   int n;
   int64_t nnz;
   int64_t* d_indptr = nullptr;
@@ -569,24 +569,21 @@ struct Setup {
 // bins (d_wipe stays NULL otherwise). n > 0 and nnz > 0.
 int upload_and_filter(Setup& u, const int64_t* indptr, const int32_t* indices,
                       const double* data, int filter, int min_nnz, int k) {
-  h3d_ctx* ctx = u.ctx;
+  HostCall& hc = u.hc;
+  h3d_ctx* ctx = hc.ctx;
   hipStream_t s = ctx->stream;
   const int n = u.n;
   const int64_t nnz = u.nnz;
-  Scratch sc{ctx};
-  u.d_indptr = sc.get<int64_t>("kr_indptr", (size_t)n + 1);
-  u.d_indices = sc.get<int32_t>("kr_indices", (size_t)nnz);
-  u.d_data = sc.get<double>("kr_data", (size_t)nnz);
-  u.d_rowof = sc.get<int32_t>("kr_rowof", (size_t)nnz);
-  u.d_keep = sc.get<int32_t>("kr_keep", (size_t)nnz + 1);
-  u.d_pos = sc.get<int32_t>("kr_pos", (size_t)nnz + 1);
-  u.d_meta = sc.get<int32_t>("kr_meta", kMetaWords);
-  int32_t* d_cnt = sc.get<int32_t>("kr_band", 2 * (size_t)n);
-  int32_t* d_wipe = sc.get<int32_t>("kr_wipe", (size_t)n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "matrix buffers");
-  HIP_TRY(hipMemcpyAsync(u.d_indptr, indptr, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(u.d_indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(u.d_data, data, (size_t)nnz * 8, hipMemcpyHostToDevice, s));
+  u.d_indptr = hc.in("kr_indptr", indptr, (size_t)n + 1);
+  u.d_indices = hc.in("kr_indices", indices, (size_t)nnz);
+  u.d_data = hc.in("kr_data", data, (size_t)nnz);
+  u.d_rowof = hc.out<int32_t>("kr_rowof", (size_t)nnz);
+  u.d_keep = hc.out<int32_t>("kr_keep", (size_t)nnz + 1);
+  u.d_pos = hc.out<int32_t>("kr_pos", (size_t)nnz + 1);
+  u.d_meta = hc.out<int32_t>("kr_meta", kMetaWords);
+  int32_t* d_cnt = hc.out<int32_t>("kr_band", 2 * (size_t)n);
+  int32_t* d_wipe = hc.out<int32_t>("kr_wipe", (size_t)n);
+  if (int rc = hc.ready("matrix buffers")) return rc;
   HIP_TRY(hipMemsetAsync(u.d_meta, 0, kMetaWords * 4, s));
   ProfScope ps(ctx, "kr_filter", nnz);
   hipLaunchKernelGGL(k_entry_rows, dim3(grid_for(ctx, nnz)), dim3(kBlock), 0, s, u.d_indptr, n,
@@ -751,15 +748,14 @@ int h3d_filter_sparse_rows(h3d_ctx* ctx, const int64_t* indptr, const int32_t* i
     if (n_wiped && filter) *n_wiped = n;  // (every count is 0 < min_nnz)
     return 0;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Setup u{ctx, n, nnz};
+  HostCall hc(ctx);
+  Setup u{hc, n, nnz};
   if (int rc = upload_and_filter(u, indptr, indices, data, filter, min_nnz, k)) return rc;
-  Scratch sc{ctx};
-  int64_t* d_oip = sc.get<int64_t>("kr_out_indptr", (size_t)n + 1);
-  int32_t* d_oidx = sc.get<int32_t>("kr_out_indices", (size_t)nnz);
-  double* d_odat = sc.get<double>("kr_out_data", (size_t)nnz);
-  if (!sc.ok) return fail(H3D_ENOMEM, "filter output");
+  int64_t* d_oip = hc.out<int64_t>("kr_out_indptr", (size_t)n + 1);
+  int32_t* d_oidx = hc.out<int32_t>("kr_out_indices", (size_t)nnz);
+  double* d_odat = hc.out<double>("kr_out_data", (size_t)nnz);
+  if (int rc = hc.ready("filter output")) return rc;
   hipLaunchKernelGGL(k_keep, dim3(grid_for(ctx, nnz + 1)), dim3(kBlock), 0, s, u.d_rowof,
                      u.d_indices, u.d_data, nnz, n, u.d_wipe, filter, 0, u.d_keep,
                      (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, u.d_meta);
@@ -772,14 +768,13 @@ int h3d_filter_sparse_rows(h3d_ctx* ctx, const int64_t* indptr, const int32_t* i
   if (int rc = d2h_sync(ctx, meta, u.d_meta, sizeof(meta), s)) return rc;
   if (meta[kMetaBadCol])
     return fail(H3D_EINPUT, "%d column indices outside [0, %d)", meta[kMetaBadCol], n);
-  HIP_TRY(hipMemcpyAsync(out_indptr, d_oip, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  // the kept count (the last row pointer) sizes the other two downloads
+  hc.back(out_indptr, d_oip, (size_t)n + 1);
+  if (int rc = hc.finish()) return rc;
   const int64_t kept = out_indptr[n];
-  if (kept > 0) {
-    HIP_TRY(hipMemcpyAsync(out_indices, d_oidx, (size_t)kept * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_data, d_odat, (size_t)kept * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
+  hc.back(out_indices, d_oidx, (size_t)kept);
+  hc.back(out_data, d_odat, (size_t)kept);
+  if (int rc = kept > 0 ? hc.finish() : 0) return rc;
   *nnz_out = kept;
   if (n_wiped) *n_wiped = meta[kMetaWiped];
   return 0;
@@ -806,13 +801,13 @@ int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
     stats[4] = filter ? n : 0;
     return 0;
   }
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Setup u{ctx, n, nnz};
+  HostCall hc(ctx);
+  Setup u{hc, n, nnz};
   if (int rc = upload_and_filter(u, indptr, indices, data, filter, min_nnz, k)) return rc;
 
   // symmetrise: keep flags and sort keys, scans, the stable sort, the fills
-  Scratch sc{ctx};
+  Scratch& sc = hc.sc;
   int32_t* d_key = sc.get<int32_t>("kr_key", (size_t)nnz);
   int32_t* d_val = sc.get<int32_t>("kr_val", (size_t)nnz);
   int32_t* d_skey = sc.get<int32_t>("kr_skey", (size_t)nnz);
@@ -824,12 +819,11 @@ int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
   double* d_fval = sc.get<double>("kr_fval", 2 * (size_t)nnz);
   double* d_vec = sc.get<double>("kr_vec", 11 * (size_t)n);
   double* d_parts = sc.get<double>("kr_parts", 6 * (size_t)kMaxParts);
-  double* d_x0 = x0 ? sc.get<double>("kr_x0", (size_t)n) : nullptr;
+  double* d_x0 = hc.in("kr_x0", x0, (size_t)n);
   KrState* d_st = sc.get<KrState>("kr_state", 1);
-  if (!sc.ok) return fail(H3D_ENOMEM, "balancing buffers");
+  if (int rc = hc.ready("balancing buffers")) return rc;
   KrState* h_st = (KrState*)pinned_rd(ctx, sizeof(KrState));
   if (!h_st) return fail(H3D_ENOMEM, "pinned record");
-  if (x0) HIP_TRY(hipMemcpyAsync(d_x0, x0, (size_t)n * 8, hipMemcpyHostToDevice, s));
   int end_bit = 1;
   while (((int64_t)1 << end_bit) <= n) ++end_bit;  // the sentinel key n fits
   int32_t meta[kMetaWords], full_nnz = 0, n_low = 0;
@@ -873,8 +867,7 @@ int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
     for (int i = 0; i < n; ++i) bias_out[i] = nan;
     if (balanced_out)
       for (int64_t e = 0; e < nnz; ++e) balanced_out[e] = 0.0;
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
+    return hc.finish();
   }
 
   Run run;
@@ -913,11 +906,9 @@ int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
                          u.d_indices, u.d_keep, nnz, d_scale, u.d_data);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(bias_out, d_bias, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  if (balanced_out)
-    HIP_TRY(hipMemcpyAsync(balanced_out, u.d_data, (size_t)nnz * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(bias_out, d_bias, (size_t)n);
+  hc.back(balanced_out, u.d_data, (size_t)nnz);
+  return hc.finish();
 }
 
 }  // extern "C"

@@ -270,17 +270,13 @@ int h3d_bh_ctx(h3d_ctx* ctx, const double* p, int64_t n, double* q) {
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (n == 0) return 0;
   if (n < 0 || !p || !q) return fail(H3D_EARG, "null argument");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_p = sc.get<double>("bh_in", n);
-  double* d_q = sc.get<double>("bh_out", n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "bh buffers");
-  HIP_TRY(hipMemcpyAsync(d_p, p, n * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_p = hc.in("bh_in", p, n);
+  double* d_q = hc.out<double>("bh_out", n);
+  if (int rc = hc.ready("bh buffers")) return rc;
   if (int rc = h3d_bh_dev(ctx, d_p, n, d_q)) return rc;
-  HIP_TRY(hipMemcpyAsync(q, d_q, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(q, d_q, n);
+  return hc.finish();
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
-// libh3d internals shared by its HIP translation units (h3d_api.hip: the hot
-// path; h3d_alt.hip: the alternative models): the context behind the C ABI's
-// opaque h3d_ctx handle and the launch helpers. Not part of the ABI.
+// libh3d internals shared by its HIP translation units: the context behind
+// the C ABI's opaque h3d_ctx handle, the launch and argument helpers and the
+// staging of the host-buffer entry points (HostCall). The bodies of what is
+// declared here live in h3d_ctx.hip (h3d_api.hip is the hot path only). Not
+// part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -211,6 +213,58 @@ struct Scratch {
   }
 };
 
+// One host-buffer entry point's staging on the ctx's device and stream:
+// uploads, the call's slots, downloads, one synchronisation. Every operation
+// enqueues at once; the first error sticks (`err`) and ready() / finish()
+// report it. A HostCall that leaves scope with a copy in flight and without
+// finish() drains the stream, so no early return leaves a copy running into
+// or out of memory the caller gets back.
+struct HostCall {
+  h3d_ctx* ctx;
+  Scratch sc;
+  int err = 0;
+  bool in_flight = false;  // a copy was enqueued and finish() has not run
+  int* d_ovf = nullptr;    // counts(): the overflow word, its host copy and
+  int ovf = 0;             // the message of a set one
+  const char* ovf_msg = nullptr;
+
+  explicit HostCall(h3d_ctx* c);  // hipSetDevice
+  HostCall(const HostCall&) = delete;
+  ~HostCall() {
+    if (in_flight) (void)hipStreamSynchronize(ctx->stream);
+  }
+  void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+  template <typename T>  // a slot of `count` elements, without a copy
+  T* out(const char* slot, size_t count) {
+    return sc.get<T>(slot, count);
+  }
+  template <typename T>  // host -> device of `count` elements into (part of) a slot
+  void up(T* d, const T* src, size_t count) {
+    if (d && src) copy(d, src, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  // a slot of count + pad elements and the upload of `count` into it; an
+  // absent (NULL) src takes no slot and gives NULL
+  template <typename T>
+  T* in(const char* slot, const T* src, size_t count, size_t pad = 0) {
+    T* d = src ? sc.get<T>(slot, count + pad) : nullptr;
+    up(d, src, count);
+    return d;
+  }
+  // raw counts, uploaded and converted to int32; a count outside [0, 2^31)
+  // fails finish() with H3D_EINPUT and `msg`
+  int32_t* counts(const int64_t* raw64, int64_t count, const char* msg);
+  template <typename T>  // device -> host of `count` elements into caller memory
+  void back(T* dst, const T* d_src, size_t count) {
+    if (dst) copy(dst, d_src, count * sizeof(T), hipMemcpyDeviceToHost);
+  }
+  // ahead of the launches: the first error, or H3D_ENOMEM "<what>"
+  int ready(const char* what);
+  // one stream synchronisation, the count check, the first error
+  int finish();
+  // the same with a small result: `bytes` into dst through pinned_rd
+  int finish(void* dst, const void* d_src, size_t bytes);
+};
+
 // hipcub's two-phase calls. op(tmp, bytes) is the hipcub call itself
 // (hipError_t(void*, size_t&)): with tmp = nullptr it only reports its temp
 // size. cub_bytes is that query alone; cub_call queries, takes the temp out
@@ -234,15 +288,11 @@ int cub_call(h3d_ctx* ctx, const char* tmp_slot, Op op) {
 
 // Raw counts arrive as int64 and every kernel reads int32. counts_to_i32
 // (enqueued on the ctx stream) clears *d_ovf and converts `count` device
-// values, setting *d_ovf where one is outside [0, 2^31); upload_counts does
-// so for a host array, through the slots "in_raw64" / "in_raw" / "ovf";
-// counts_ovf_copy enqueues the word's copy into *h_ovf, which the caller
-// tests after its next stream synchronisation (H3D_EINPUT).
+// values, setting *d_ovf where one is outside [0, 2^31); HostCall::counts
+// does so for a host array, through the slots "in_raw64" / "in_raw" / "ovf",
+// and HostCall::finish reads the word (H3D_EINPUT).
 int counts_to_i32(h3d_ctx* ctx, const int64_t* d_raw64, int32_t* d_raw, int64_t count,
                   int* d_ovf);
-int upload_counts(h3d_ctx* ctx, const int64_t* raw64, int64_t count, int32_t** d_raw,
-                  int** d_ovf);
-int counts_ovf_copy(h3d_ctx* ctx, const int* d_ovf, int* h_ovf);
 hipEvent_t ev_get(h3d_ctx* ctx);
 // host -> device copy of `bytes` through the ctx's pinned bounce buffer,
 // stream-ordered on s (the source may be reused at once)
@@ -263,6 +313,11 @@ int check_cond(const int32_t* cond_of_rep, int R, int C, std::vector<int>* nrep,
                std::vector<int32_t>* rep_idx);
 // kernel status flags -> H3D_E* code (+ message)
 int flags_to_code(int fl);
+// ctx not NULL and n in [0, 2^31)
+int check_count(const void* ctx, int64_t n);
+// lets `kernel` take up to `bytes` of dynamic LDS: set once per process and
+// device, a no-op afterwards
+int allow_dynamic_lds(h3d_ctx* ctx, const void* kernel, int bytes);
 // the device table of h3d_disp_tables_dev (h3d_table.hip): copy its status
 // (before the stream sync), settle it (after): 1 = redone on the host
 int table_status_copy(h3d_ctx* ctx, int* h_st);

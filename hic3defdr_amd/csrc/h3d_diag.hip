@@ -33,6 +33,7 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_devutil.h"
 #include "h3d_errors.h"
 #include "h3d_model.h"
 
@@ -55,7 +56,6 @@ constexpr int kTile = 128;       // rows per LDS tile of deviations
 constexpr int kTileLd = kTile + 1;  // its LDS row stride (columns on distinct banks)
 constexpr int kSuper = 8192;     // rows per partial product sum (kTile | kSuper)
 constexpr int kMaxPairs = kMaxCorr * (kMaxCorr + 1) / 2;
-constexpr int64_t kMaxN = ((int64_t)1 << 31) - 1;
 
 struct Reps {
   int32_t r[h3d::kMaxReps];
@@ -193,11 +193,14 @@ int launch_group_sums(h3d_ctx* ctx, const int32_t* d_keys, const double* d_value
   return 0;
 }
 
-int check_group_sums(const void* ctx, int64_t n, int K, int C) {
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (n < 0 || n > kMaxN) return fail(H3D_EARG, "n=%lld outside [0, 2^31)", (long long)n);
+// the argument checks of h3d_group_sums and its _dev twin
+int check_group_sums(const void* ctx, const void* keys, const void* values, int64_t n, int K,
+                     int C, const void* sums, const void* counts) {
+  if (int rc = check_count(ctx, n)) return rc;
   if (K < 1 || K > kMaxKeys) return fail(H3D_EARG, "K=%d outside [1, %d]", K, kMaxKeys);
   if (C < 1 || C > kMaxCols) return fail(H3D_EARG, "C=%d outside [1, %d]", C, kMaxCols);
+  if (!sums || !counts) return fail(H3D_EARG, "null output");
+  if (n > 0 && (!keys || !values)) return fail(H3D_EARG, "null keys / values");
   return 0;
 }
 
@@ -251,13 +254,8 @@ int launch_histogram(h3d_ctx* ctx, const double* d_values, int64_t n, const doub
   if (int rc = h2d_pinned(ctx, d_edges, edges, (size_t)E * 8, s)) return rc;
   HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)(E - 1) * 8, s));
   if (n == 0) return 0;
-  static int attr = 0;
-  if (!attr) {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_histogram,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)hist_lds(kMaxEdges)));
-    attr = 1;
-  }
+  if (int rc = allow_dynamic_lds(ctx, (const void*)k_histogram, (int)hist_lds(kMaxEdges)))
+    return rc;
   ProfScope ps(ctx, "diag_histogram", n);
   hipLaunchKernelGGL(k_histogram, dim3(grid_for(ctx, n, 4)), dim3(kBlock), hist_lds(E), s,
                      d_values, n, d_edges, E, (unsigned long long*)d_counts);
@@ -344,8 +342,7 @@ __global__ __launch_bounds__(kBlock) void k_rank_keys(const double* __restrict__
        i += (int64_t)gridDim.x * kBlock) {
     const double x = v[i];
     if (x != x) bad = 1;
-    uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-    keys[i] = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    keys[i] = asc_key(x);
     idx[i] = (int32_t)i;
   }
   if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, 1);
@@ -624,9 +621,13 @@ __global__ __launch_bounds__(kBlock) void k_balance_pixels(
   }
 }
 
-int check_n(const void* ctx, int64_t n) {
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (n < 0 || n > kMaxN) return fail(H3D_EARG, "n=%lld outside [0, 2^31)", (long long)n);
+// the argument checks of h3d_histogram and its _dev twin
+int check_histogram(const void* ctx, const void* values, int64_t n, const double* edges, int E,
+                    const void* counts) {
+  if (int rc = check_count(ctx, n)) return rc;
+  if (int rc = check_edges(edges, E, "edges")) return rc;
+  if (!counts) return fail(H3D_EARG, "null output");
+  if (n > 0 && !values) return fail(H3D_EARG, "null values");
   return 0;
 }
 
@@ -637,9 +638,7 @@ extern "C" {
 int h3d_group_sums_dev(h3d_ctx* ctx, const int32_t* d_keys, const double* d_values, int64_t n,
                        int K, int C, double* d_sums, int64_t* d_counts) {
   using namespace h3ddiag;
-  if (int rc = check_group_sums(ctx, n, K, C)) return rc;
-  if (!d_sums || !d_counts) return fail(H3D_EARG, "null output");
-  if (n > 0 && (!d_keys || !d_values)) return fail(H3D_EARG, "null keys / values");
+  if (int rc = check_group_sums(ctx, d_keys, d_values, n, K, C, d_sums, d_counts)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   if (int rc = launch_group_sums(ctx, d_keys, d_values, n, K, C, d_sums, d_counts)) return rc;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -649,35 +648,25 @@ int h3d_group_sums_dev(h3d_ctx* ctx, const int32_t* d_keys, const double* d_valu
 int h3d_group_sums(h3d_ctx* ctx, const int32_t* keys, const double* values, int64_t n, int K,
                    int C, double* sums, int64_t* counts) {
   using namespace h3ddiag;
-  if (int rc = check_group_sums(ctx, n, K, C)) return rc;
-  if (!sums || !counts) return fail(H3D_EARG, "null output");
-  if (n > 0 && (!keys || !values)) return fail(H3D_EARG, "null keys / values");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  int32_t* d_keys = sc.get<int32_t>("diag_in_keys", (size_t)n + 1);
-  double* d_values = sc.get<double>("diag_in_a", (size_t)n * C + 1);
-  double* d_sums = sc.get<double>("diag_out_a", (size_t)K * C);
-  int64_t* d_counts = sc.get<int64_t>("diag_out_i", (size_t)K);
-  if (!sc.ok) return fail(H3D_ENOMEM, "group sums buffers");
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d_keys, keys, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_values, values, (size_t)n * C * 8, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = check_group_sums(ctx, keys, values, n, K, C, sums, counts)) return rc;
+  HostCall hc(ctx);
+  int32_t* d_keys = hc.out<int32_t>("diag_in_keys", (size_t)n + 1);
+  double* d_values = hc.out<double>("diag_in_a", (size_t)n * C + 1);
+  double* d_sums = hc.out<double>("diag_out_a", (size_t)K * C);
+  int64_t* d_counts = hc.out<int64_t>("diag_out_i", (size_t)K);
+  if (int rc = hc.ready("group sums buffers")) return rc;
+  hc.up(d_keys, keys, (size_t)n);
+  hc.up(d_values, values, (size_t)n * C);
   if (int rc = launch_group_sums(ctx, d_keys, d_values, n, K, C, d_sums, d_counts)) return rc;
-  HIP_TRY(hipMemcpyAsync(sums, d_sums, (size_t)K * C * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)K * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(sums, d_sums, (size_t)K * C);
+  hc.back(counts, d_counts, (size_t)K);
+  return hc.finish();
 }
 
 int h3d_histogram_dev(h3d_ctx* ctx, const double* d_values, int64_t n, const double* edges,
                       int E, int64_t* d_counts) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
-  if (int rc = check_edges(edges, E, "edges")) return rc;
-  if (!d_counts) return fail(H3D_EARG, "null output");
-  if (n > 0 && !d_values) return fail(H3D_EARG, "null values");
+  if (int rc = check_histogram(ctx, d_values, n, edges, E, d_counts)) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   if (int rc = launch_histogram(ctx, d_values, n, edges, E, d_counts)) return rc;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -687,28 +676,22 @@ int h3d_histogram_dev(h3d_ctx* ctx, const double* d_values, int64_t n, const dou
 int h3d_histogram(h3d_ctx* ctx, const double* values, int64_t n, const double* edges, int E,
                   int64_t* counts) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
-  if (int rc = check_edges(edges, E, "edges")) return rc;
-  if (!counts) return fail(H3D_EARG, "null output");
-  if (n > 0 && !values) return fail(H3D_EARG, "null values");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_values = sc.get<double>("diag_in_a", (size_t)n + 1);
-  int64_t* d_counts = sc.get<int64_t>("diag_out_i", (size_t)kMaxEdges);
-  if (!sc.ok) return fail(H3D_ENOMEM, "histogram buffers");
-  if (n > 0) HIP_TRY(hipMemcpyAsync(d_values, values, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  if (int rc = check_histogram(ctx, values, n, edges, E, counts)) return rc;
+  HostCall hc(ctx);
+  double* d_values = hc.out<double>("diag_in_a", (size_t)n + 1);
+  int64_t* d_counts = hc.out<int64_t>("diag_out_i", (size_t)kMaxEdges);
+  if (int rc = hc.ready("histogram buffers")) return rc;
+  hc.up(d_values, values, (size_t)n);
   if (int rc = launch_histogram(ctx, d_values, n, edges, E, d_counts)) return rc;
-  HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)(E - 1) * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(counts, d_counts, (size_t)(E - 1));
+  return hc.finish();
 }
 
 int h3d_density_grid(h3d_ctx* ctx, const double* x, const double* y, const int8_t* label,
                      int64_t n, int L, const double* xedges, int Ex, const double* yedges,
                      int Ey, int64_t* counts) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_count(ctx, n)) return rc;
   if (L < 1 || L > 127) return fail(H3D_EARG, "L=%d outside [1, 127]", L);
   if (int rc = check_edges(xedges, Ex, "xedges")) return rc;
   if (int rc = check_edges(yedges, Ey, "yedges")) return rc;
@@ -717,38 +700,30 @@ int h3d_density_grid(h3d_ctx* ctx, const double* x, const double* y, const int8_
   const int64_t cells = (int64_t)L * (Ex - 1) * (Ey - 1);
   if (cells >= ((int64_t)1 << 28))
     return fail(H3D_EARG, "L * (Ex - 1) * (Ey - 1) = %lld is not below 2^28", (long long)cells);
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_x = sc.get<double>("diag_in_a", (size_t)n + 1);
-  double* d_y = sc.get<double>("diag_in_b", (size_t)n + 1);
-  int8_t* d_label = sc.get<int8_t>("diag_in_l", (size_t)n + 1);
-  double* d_edges = sc.get<double>("diag_edges2", (size_t)2 * kMaxEdges);
-  int64_t* d_counts = sc.get<int64_t>("diag_out_grid", (size_t)cells);
-  if (!sc.ok) return fail(H3D_ENOMEM, "density grid buffers");
+  HostCall hc(ctx);
+  double* d_x = hc.out<double>("diag_in_a", (size_t)n + 1);
+  double* d_y = hc.out<double>("diag_in_b", (size_t)n + 1);
+  int8_t* d_label = hc.out<int8_t>("diag_in_l", (size_t)n + 1);
+  double* d_edges = hc.out<double>("diag_edges2", (size_t)2 * kMaxEdges);
+  int64_t* d_counts = hc.out<int64_t>("diag_out_grid", (size_t)cells);
+  if (int rc = hc.ready("density grid buffers")) return rc;
   HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)cells * 8, s));
   if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_y, y, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_label, label, (size_t)n, hipMemcpyHostToDevice, s));
+    hc.up(d_x, x, (size_t)n);
+    hc.up(d_y, y, (size_t)n);
+    hc.up(d_label, label, (size_t)n);
     if (int rc = h2d_pinned(ctx, d_edges, xedges, (size_t)Ex * 8, s)) return rc;
     if (int rc = h2d_pinned(ctx, d_edges + Ex, yedges, (size_t)Ey * 8, s)) return rc;
-    static int attr = 0;
-    if (!attr) {
-      HIP_TRY(hipFuncSetAttribute((const void*)k_density,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * kMaxEdges * 8));
-      attr = 1;
-    }
+    if (int rc = allow_dynamic_lds(ctx, (const void*)k_density, 2 * kMaxEdges * 8)) return rc;
     ProfScope ps(ctx, "diag_density_grid", n);
     hipLaunchKernelGGL(k_density, dim3(grid_for(ctx, n, 4)), dim3(kBlock),
                        (size_t)(Ex + Ey) * 8, s, d_x, d_y, d_label, n, L, d_edges, Ex, Ey,
                        (unsigned long long*)d_counts);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)cells * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(counts, d_counts, (size_t)cells);
+  return hc.finish();
 }
 
 int h3d_ma_stats(h3d_ctx* ctx, const double* scaled, int64_t n, int R, int C,
@@ -756,7 +731,7 @@ int h3d_ma_stats(h3d_ctx* ctx, const double* scaled, int64_t n, int R, int C,
                  const double* qvalues, int64_t n_q, double fdr, double* mean, double* m,
                  double* a, int8_t* label) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_count(ctx, n)) return rc;
   if (!cond_of_rep) return fail(H3D_EARG, "null cond_of_rep");
   std::vector<int> nrep;
   std::vector<int32_t> rep_idx;
@@ -774,21 +749,18 @@ int h3d_ma_stats(h3d_ctx* ctx, const double* scaled, int64_t n, int R, int C,
   Reps r0{}, r1{};
   for (int k = 0; k < nrep[cond0]; ++k) r0.r[k] = rep_idx[(size_t)cond0 * h3d::kMaxReps + k];
   for (int k = 0; k < nrep[cond1]; ++k) r1.r[k] = rep_idx[(size_t)cond1 * h3d::kMaxReps + k];
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_scaled = sc.get<double>("diag_in_a", (size_t)n * R);
-  double* d_q = sc.get<double>("diag_in_b", (size_t)n_q + 1);
-  uint8_t* d_loop = loop_idx ? (uint8_t*)sc.get<int8_t>("diag_in_l", (size_t)n) : nullptr;
-  int32_t* d_flag = loop_idx ? sc.get<int32_t>("diag_head", (size_t)n) : nullptr;
-  int32_t* d_qpos = loop_idx ? sc.get<int32_t>("diag_run_of", (size_t)n) : nullptr;
-  double* d_out = sc.get<double>("diag_out_a", (size_t)n * 4);  // mean (n, 2) | m | a
-  int8_t* d_label = sc.get<int8_t>("diag_out_l", (size_t)n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "ma_stats buffers");
-  HIP_TRY(hipMemcpyAsync(d_scaled, scaled, (size_t)n * R * 8, hipMemcpyHostToDevice, s));
-  if (n_q > 0) HIP_TRY(hipMemcpyAsync(d_q, qvalues, (size_t)n_q * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_scaled = hc.in("diag_in_a", scaled, (size_t)n * R);
+  double* d_q = hc.out<double>("diag_in_b", (size_t)n_q + 1);
+  hc.up(d_q, qvalues, (size_t)n_q);
+  uint8_t* d_loop = (uint8_t*)hc.in("diag_in_l", (const int8_t*)loop_idx, (size_t)n);
+  int32_t* d_flag = loop_idx ? hc.out<int32_t>("diag_head", (size_t)n) : nullptr;
+  int32_t* d_qpos = loop_idx ? hc.out<int32_t>("diag_run_of", (size_t)n) : nullptr;
+  double* d_out = hc.out<double>("diag_out_a", (size_t)n * 4);  // mean (n, 2) | m | a
+  int8_t* d_label = hc.out<int8_t>("diag_out_l", (size_t)n);
+  if (int rc = hc.ready("ma_stats buffers")) return rc;
   if (loop_idx) {
-    HIP_TRY(hipMemcpyAsync(d_loop, loop_idx, (size_t)n, hipMemcpyHostToDevice, s));
     ProfScope ps(ctx, "diag_ma_scan", n);
     hipLaunchKernelGGL(k_flag_to_int, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_loop, n,
                        d_flag);
@@ -812,69 +784,60 @@ int h3d_ma_stats(h3d_ctx* ctx, const double* scaled, int64_t n, int R, int C,
                        d_out + 2 * n, d_out + 3 * n, d_label);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(mean, d_out, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(m, d_out + 2 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(a, d_out + 3 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(label, d_label, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(mean, d_out, (size_t)n * 2);
+  hc.back(m, d_out + 2 * n, (size_t)n);
+  hc.back(a, d_out + 3 * n, (size_t)n);
+  hc.back(label, d_label, (size_t)n);
+  return hc.finish();
 }
 
 int h3d_rank_average(h3d_ctx* ctx, const double* values, int64_t n, int R, double* ranks,
                      int32_t* nan_flags) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_count(ctx, n)) return rc;
   if (R < 1 || R > kMaxCorr) return fail(H3D_EARG, "R=%d outside [1, %d]", R, kMaxCorr);
   if (!nan_flags) return fail(H3D_EARG, "null flags");
   if (n > 0 && (!values || !ranks)) return fail(H3D_EARG, "null values / ranks");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_values = sc.get<double>("diag_in_a", (size_t)n * R + 1);
-  double* d_ranks = sc.get<double>("diag_out_a", (size_t)n * R + 1);
-  int* d_flags = sc.get<int>("diag_rank_flags", (size_t)kMaxCorr);
-  if (!sc.ok) return fail(H3D_ENOMEM, "rank buffers");
-  if (n > 0)
-    HIP_TRY(hipMemcpyAsync(d_values, values, (size_t)n * R * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_values = hc.out<double>("diag_in_a", (size_t)n * R + 1);
+  double* d_ranks = hc.out<double>("diag_out_a", (size_t)n * R + 1);
+  int* d_flags = hc.out<int>("diag_rank_flags", (size_t)kMaxCorr);
+  if (int rc = hc.ready("rank buffers")) return rc;
+  hc.up(d_values, values, (size_t)n * R);
   if (int rc = launch_rank_average(ctx, d_values, n, R, d_ranks, d_flags)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(ranks, d_ranks, (size_t)n * R * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(nan_flags, d_flags, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(ranks, d_ranks, (size_t)n * R);
+  hc.back(nan_flags, d_flags, (size_t)R);
+  return hc.finish();
 }
 
 int h3d_corr_matrix(h3d_ctx* ctx, const double* values, int64_t n, int R, int ranked,
                     double* corr) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_count(ctx, n)) return rc;
   if (R < 1 || R > kMaxCorr) return fail(H3D_EARG, "R=%d outside [1, %d]", R, kMaxCorr);
   if (!corr) return fail(H3D_EARG, "null output");
   if (n > 0 && !values) return fail(H3D_EARG, "null values");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_values = sc.get<double>("diag_in_a", (size_t)n * R + 1);
-  double* d_ranks = ranked ? sc.get<double>("diag_out_a", (size_t)n * R + 1) : nullptr;
-  int* d_flags = sc.get<int>("diag_rank_flags", (size_t)kMaxCorr);
-  double* d_corr = sc.get<double>("diag_out_corr", (size_t)kMaxCorr * kMaxCorr);
-  if (!sc.ok) return fail(H3D_ENOMEM, "correlation buffers");
-  if (n > 0)
-    HIP_TRY(hipMemcpyAsync(d_values, values, (size_t)n * R * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_values = hc.out<double>("diag_in_a", (size_t)n * R + 1);
+  double* d_ranks = ranked ? hc.out<double>("diag_out_a", (size_t)n * R + 1) : nullptr;
+  int* d_flags = hc.out<int>("diag_rank_flags", (size_t)kMaxCorr);
+  double* d_corr = hc.out<double>("diag_out_corr", (size_t)kMaxCorr * kMaxCorr);
+  if (int rc = hc.ready("correlation buffers")) return rc;
+  hc.up(d_values, values, (size_t)n * R);
   const double* src = d_values;
   if (ranked) {  // Spearman: Pearson of the average ranks
     if (int rc = launch_rank_average(ctx, d_values, n, R, d_ranks, d_flags)) return rc;
     src = d_ranks;
   }
   if (int rc = launch_corr(ctx, src, n, R, d_corr)) return rc;
-  HIP_TRY(hipMemcpyAsync(corr, d_corr, (size_t)R * R * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(corr, d_corr, (size_t)R * R);
+  return hc.finish();
 }
 
 int h3d_pixel_moments(h3d_ctx* ctx, const double* scaled, int64_t n, int R, const int32_t* reps,
                       int n_reps, double* mean, double* var) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_count(ctx, n)) return rc;
   if (R < 1 || R > h3d::kMaxReps) return fail(H3D_EARG, "R=%d outside [1, %d]", R, h3d::kMaxReps);
   if (!reps || n_reps < 1 || n_reps > R)
     return fail(H3D_EARG, "%d replicates of R=%d", n_reps, R);
@@ -885,57 +848,47 @@ int h3d_pixel_moments(h3d_ctx* ctx, const double* scaled, int64_t n, int R, cons
   }
   if (n == 0) return 0;
   if (!scaled || !mean || !var) return fail(H3D_EARG, "null input / output");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_scaled = sc.get<double>("diag_in_a", (size_t)n * R);
-  double* d_out = sc.get<double>("diag_out_a", (size_t)n * 2);
-  if (!sc.ok) return fail(H3D_ENOMEM, "pixel moments buffers");
-  HIP_TRY(hipMemcpyAsync(d_scaled, scaled, (size_t)n * R * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_scaled = hc.in("diag_in_a", scaled, (size_t)n * R);
+  double* d_out = hc.out<double>("diag_out_a", (size_t)n * 2);  // mean | var
+  if (int rc = hc.ready("pixel moments buffers")) return rc;
   {
     ProfScope ps(ctx, "diag_pixel_moments", n);
-    hipLaunchKernelGGL(k_pixel_moments, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_scaled, n,
-                       R, rr, n_reps, d_out, d_out + n);
+    hipLaunchKernelGGL(k_pixel_moments, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream,
+                       d_scaled, n, R, rr, n_reps, d_out, d_out + n);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(mean, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(var, d_out + n, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(mean, d_out, (size_t)n);
+  hc.back(var, d_out + n, (size_t)n);
+  return hc.finish();
 }
 
 int h3d_balance_pixels(h3d_ctx* ctx, const int32_t* row, const int32_t* col, const int64_t* raw,
                        const double* bias, int64_t n, int R, int n_bins, double* balanced) {
   using namespace h3ddiag;
-  if (int rc = check_n(ctx, n)) return rc;
+  if (int rc = check_count(ctx, n)) return rc;
   if (R < 1 || R > h3d::kMaxReps) return fail(H3D_EARG, "R=%d outside [1, %d]", R, h3d::kMaxReps);
   if (n_bins < 0) return fail(H3D_EARG, "n_bins=%d", n_bins);
   if (n == 0) return 0;
   if (!row || !col || !raw || !balanced) return fail(H3D_EARG, "null input / output");
   if (n_bins > 0 && !bias) return fail(H3D_EARG, "null bias");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  int32_t* d_row = sc.get<int32_t>("diag_idx", (size_t)n + 1);
-  int32_t* d_col = sc.get<int32_t>("diag_idx_s", (size_t)n + 1);
-  int64_t* d_raw = (int64_t*)sc.get<double>("diag_in_a", (size_t)n * R);
-  double* d_bias = sc.get<double>("diag_in_b", (size_t)n_bins * R + 1);
-  double* d_out = sc.get<double>("diag_out_a", (size_t)n * R);
-  if (!sc.ok) return fail(H3D_ENOMEM, "balance buffers");
-  HIP_TRY(hipMemcpyAsync(d_row, row, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_col, col, (size_t)n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_raw, raw, (size_t)n * R * 8, hipMemcpyHostToDevice, s));
-  if (n_bins > 0)
-    HIP_TRY(hipMemcpyAsync(d_bias, bias, (size_t)n_bins * R * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  int32_t* d_row = hc.in("diag_idx", row, (size_t)n, 1);
+  int32_t* d_col = hc.in("diag_idx_s", col, (size_t)n, 1);
+  int64_t* d_raw = (int64_t*)hc.out<double>("diag_in_a", (size_t)n * R);
+  hc.up(d_raw, raw, (size_t)n * R);
+  double* d_bias = hc.out<double>("diag_in_b", (size_t)n_bins * R + 1);
+  hc.up(d_bias, bias, (size_t)n_bins * R);
+  double* d_out = hc.out<double>("diag_out_a", (size_t)n * R);
+  if (int rc = hc.ready("balance buffers")) return rc;
   {
     ProfScope ps(ctx, "diag_balance_pixels", n * R);
-    hipLaunchKernelGGL(k_balance_pixels, dim3(grid_for(ctx, n * R)), dim3(kBlock), 0, s, d_row,
-                       d_col, d_raw, d_bias, n, R, n_bins, d_out);
+    hipLaunchKernelGGL(k_balance_pixels, dim3(grid_for(ctx, n * R)), dim3(kBlock), 0, ctx->stream,
+                       d_row, d_col, d_raw, d_bias, n, R, n_bins, d_out);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(balanced, d_out, (size_t)n * R * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(balanced, d_out, (size_t)n * R);
+  return hc.finish();
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_devutil.h"
 #include "h3d_errors.h"
 
 using namespace h3dint;
@@ -35,17 +36,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kMaxRanks = 64;   // K of h3d_order_stats
 constexpr int kMaxRanges = 64;  // B of h3d_bin_fractions: one lane per range
 constexpr int64_t kMaxN = ((int64_t)1 << 31) - 1;
-constexpr uint64_t kSign = 0x8000000000000000ull;
-
-// order-preserving key of a double, ascending (-0.0 and +0.0 one value, as
-// k_rank_keys of h3d_diag.hip), and its inverse
-__device__ inline uint64_t asc_key(double x) {
-  const uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | kSign);
-}
-__device__ inline double asc_value(uint64_t k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & ~kSign) : ~k));
-}
 
 // the block's sum of v, valid in thread 0
 __device__ inline int block_sum(int v) {
@@ -129,10 +119,15 @@ int launch_membership(h3d_ctx* ctx, const int64_t* d_row, const int64_t* d_col, 
   return d2h_sync(ctx, h_flag, d_flag, sizeof(int), s);
 }
 
-int check_membership(const void* ctx, int64_t n, int64_t k) {
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (n < 0 || n > kMaxN) return fail(H3D_EARG, "n=%lld outside [0, 2^31)", (long long)n);
+// both membership entry points' checks: 0 = run it, 1 = n or k is 0, < 0 = an error
+int check_membership(const void* ctx, const void* row, const void* col, int64_t n,
+                     const void* prow, const void* pcol, int64_t k, const void* out) {
+  if (int rc = check_count(ctx, n)) return rc;
   if (k < 0 || k > kMaxN) return fail(H3D_EARG, "k=%lld outside [0, 2^31)", (long long)k);
+  if (n == 0) return 1;
+  if (!row || !col || !out) return fail(H3D_EARG, "null query / output");
+  if (k == 0) return 1;
+  if (!prow || !pcol) return fail(H3D_EARG, "null set");
   return 0;
 }
 
@@ -330,12 +325,14 @@ int launch_roc(h3d_ctx* ctx, const uint8_t* d_labels, const double* d_scores, in
   return 0;
 }
 
+// both roc entry points' checks (have_bufs: no input or output array is NULL)
 int check_roc(const void* ctx, int64_t n, int64_t n_fdr_points, const void* m_out,
-              const void* flags) {
+              const void* flags, bool have_bufs) {
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (n < 1 || n > kMaxN) return fail(H3D_EARG, "n=%lld outside [1, 2^31)", (long long)n);
   if (n_fdr_points < 1) return fail(H3D_EARG, "n_fdr_points=%lld", (long long)n_fdr_points);
   if (!m_out || !flags) return fail(H3D_EARG, "null m_out / flags");
+  if (!have_bufs) return fail(H3D_EARG, "null argument");
   return 0;
 }
 
@@ -442,19 +439,17 @@ int h3d_pixel_membership_dev(h3d_ctx* ctx, const int64_t* d_row, const int64_t* 
                              const int64_t* d_prow, const int64_t* d_pcol, int64_t k,
                              uint8_t* d_out) {
   using namespace h3deval;
-  if (int rc = check_membership(ctx, n, k)) return rc;
-  if (n == 0) return 0;
-  if (!d_row || !d_col || !d_out) return fail(H3D_EARG, "null query / output");
+  const int rc = check_membership(ctx, d_row, d_col, n, d_prow, d_pcol, k, d_out);
+  if (rc < 0 || n == 0) return rc < 0 ? rc : 0;
   HIP_TRY(hipSetDevice(ctx->device));
   if (k == 0) {
     HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)n, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
   }
-  if (!d_prow || !d_pcol) return fail(H3D_EARG, "null set");
   int flag = 0;
-  if (int rc = launch_membership(ctx, d_row, d_col, n, d_prow, d_pcol, k, d_out, &flag))
-    return rc;
+  if (int lrc = launch_membership(ctx, d_row, d_col, n, d_prow, d_pcol, k, d_out, &flag))
+    return lrc;
   if (flag) return fail(H3D_EARG, "a query pixel has a coordinate outside [0, 2^31)");
   return 0;
 }
@@ -462,34 +457,25 @@ int h3d_pixel_membership_dev(h3d_ctx* ctx, const int64_t* d_row, const int64_t* 
 int h3d_pixel_membership(h3d_ctx* ctx, const int64_t* row, const int64_t* col, int64_t n,
                          const int64_t* prow, const int64_t* pcol, int64_t k, uint8_t* out) {
   using namespace h3deval;
-  if (int rc = check_membership(ctx, n, k)) return rc;
-  if (n == 0) return 0;
-  if (!row || !col || !out) return fail(H3D_EARG, "null query / output");
+  const int rc = check_membership(ctx, row, col, n, prow, pcol, k, out);
+  if (rc < 0 || n == 0) return rc < 0 ? rc : 0;
   if (k == 0) {
     std::memset(out, 0, (size_t)n);
     return 0;
   }
-  if (!prow || !pcol) return fail(H3D_EARG, "null set");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  int64_t* d_row = sc.get<int64_t>("eval_in_row", (size_t)n);
-  int64_t* d_col = sc.get<int64_t>("eval_in_col", (size_t)n);
-  int64_t* d_prow = sc.get<int64_t>("eval_in_prow", (size_t)k);
-  int64_t* d_pcol = sc.get<int64_t>("eval_in_pcol", (size_t)k);
-  uint8_t* d_out = sc.get<uint8_t>("eval_out_b", (size_t)n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "membership buffers");
-  HIP_TRY(hipMemcpyAsync(d_row, row, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_col, col, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_prow, prow, (size_t)k * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_pcol, pcol, (size_t)k * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  int64_t* d_row = hc.in("eval_in_row", row, (size_t)n);
+  int64_t* d_col = hc.in("eval_in_col", col, (size_t)n);
+  int64_t* d_prow = hc.in("eval_in_prow", prow, (size_t)k);
+  int64_t* d_pcol = hc.in("eval_in_pcol", pcol, (size_t)k);
+  uint8_t* d_out = hc.out<uint8_t>("eval_out_b", (size_t)n);
+  if (int arc = hc.ready("membership buffers")) return arc;
   int flag = 0;
-  if (int rc = launch_membership(ctx, d_row, d_col, n, d_prow, d_pcol, k, d_out, &flag))
-    return rc;
+  if (int lrc = launch_membership(ctx, d_row, d_col, n, d_prow, d_pcol, k, d_out, &flag))
+    return lrc;
   if (flag) return fail(H3D_EARG, "a query pixel has a coordinate outside [0, 2^31)");
-  HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(out, d_out, (size_t)n);
+  return hc.finish();
 }
 
 int h3d_roc_curve_dev(h3d_ctx* ctx, const uint8_t* d_labels, const double* d_scores, int64_t n,
@@ -497,9 +483,10 @@ int h3d_roc_curve_dev(h3d_ctx* ctx, const uint8_t* d_labels, const double* d_sco
                       double* d_fdr, double* d_fpr, double* d_tpr, double* d_thresh,
                       int64_t* d_fps, int64_t* d_tps, int64_t* m_out, int* flags) {
   using namespace h3deval;
-  if (int rc = check_roc(ctx, n, n_fdr_points, m_out, flags)) return rc;
-  if (!d_labels || !d_scores || !d_fdr || !d_fpr || !d_tpr || !d_thresh || !d_fps || !d_tps)
-    return fail(H3D_EARG, "null argument");
+  if (int rc = check_roc(ctx, n, n_fdr_points, m_out, flags,
+                         d_labels && d_scores && d_fdr && d_fpr && d_tpr && d_thresh &&
+                             d_fps && d_tps))
+    return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   int64_t* d_st = (int64_t*)scratch(ctx, "eval_status", 16);
   if (!d_st) return fail(H3D_ENOMEM, "roc status");
@@ -515,44 +502,38 @@ int h3d_roc_curve(h3d_ctx* ctx, const uint8_t* labels, const double* scores, int
                   double* fpr, double* tpr, double* thresh, int64_t* fps, int64_t* tps,
                   int64_t* m_out, int* flags) {
   using namespace h3deval;
-  if (int rc = check_roc(ctx, n, n_fdr_points, m_out, flags)) return rc;
-  if (!labels || !scores || !fdr || !fpr || !tpr || !thresh || !fps || !tps)
-    return fail(H3D_EARG, "null argument");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  uint8_t* d_labels = sc.get<uint8_t>("eval_in_lab", (size_t)n);
-  double* d_scores = sc.get<double>("eval_in_score", (size_t)n);
+  if (int rc = check_roc(ctx, n, n_fdr_points, m_out, flags,
+                         labels && scores && fdr && fpr && tpr && thresh && fps && tps))
+    return rc;
+  HostCall hc(ctx);
+  uint8_t* d_labels = hc.in("eval_in_lab", labels, (size_t)n);
+  double* d_scores = hc.in("eval_in_score", scores, (size_t)n);
   // fdr, fpr, tpr, thresh, fps, tps: six arrays of n + 1 words in one slot
   const size_t cap = (size_t)n + 1;
-  double* d_out = sc.get<double>("eval_out_roc", 6 * cap);
-  int64_t* d_st = sc.get<int64_t>("eval_status", 2);
-  if (!sc.ok) return fail(H3D_ENOMEM, "roc buffers");
+  double* d_out = hc.out<double>("eval_out_roc", 6 * cap);
+  int64_t* d_st = hc.out<int64_t>("eval_status", 2);
+  if (int rc = hc.ready("roc buffers")) return rc;
   int64_t* d_fps = (int64_t*)(d_out + 4 * cap);
   int64_t* d_tps = (int64_t*)(d_out + 5 * cap);
-  HIP_TRY(hipMemcpyAsync(d_labels, labels, (size_t)n, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_scores, scores, (size_t)n * 8, hipMemcpyHostToDevice, s));
   if (int rc = launch_roc(ctx, d_labels, d_scores, n, n_fdr_points, drop_intermediate,
                           complement, d_out, d_out + cap, d_out + 2 * cap, d_out + 3 * cap,
                           d_fps, d_tps, d_st, (int*)(d_st + 1)))
     return rc;
   if (int rc = roc_status(ctx, d_st, (int*)(d_st + 1), n, m_out, flags)) return rc;
-  const size_t mb = (size_t)*m_out * 8;
-  HIP_TRY(hipMemcpyAsync(fdr, d_out, mb, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(fpr, d_out + cap, mb, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(tpr, d_out + 2 * cap, mb, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(thresh, d_out + 3 * cap, mb, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(fps, d_fps, mb, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(tps, d_tps, mb, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  const size_t m = (size_t)*m_out;
+  hc.back(fdr, d_out, m);
+  hc.back(fpr, d_out + cap, m);
+  hc.back(tpr, d_out + 2 * cap, m);
+  hc.back(thresh, d_out + 3 * cap, m);
+  hc.back(fps, d_fps, m);
+  hc.back(tps, d_tps, m);
+  return hc.finish();
 }
 
 int h3d_order_stats(h3d_ctx* ctx, const double* values, int64_t n, const int64_t* ranks, int K,
                     double* out, int64_t* nan_count) {
   using namespace h3deval;
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (n < 0 || n > kMaxN) return fail(H3D_EARG, "n=%lld outside [0, 2^31)", (long long)n);
+  if (int rc = check_count(ctx, n)) return rc;
   if (K < 0 || K > kMaxRanks) return fail(H3D_EARG, "K=%d outside [0, %d]", K, kMaxRanks);
   if (!nan_count || (K > 0 && (!ranks || !out))) return fail(H3D_EARG, "null argument");
   Ranks rk;
@@ -565,17 +546,15 @@ int h3d_order_stats(h3d_ctx* ctx, const double* values, int64_t n, const int64_t
   *nan_count = 0;
   if (n == 0) return 0;
   if (!values) return fail(H3D_EARG, "null values");
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_v = sc.get<double>("eval_in_score", (size_t)n);
-  uint64_t* keys = sc.get<uint64_t>("eval_rk", (size_t)n);
-  uint64_t* keys_s = sc.get<uint64_t>("eval_rk_s", (size_t)n);
+  HostCall hc(ctx);
+  double* d_v = hc.in("eval_in_score", values, (size_t)n);
+  uint64_t* keys = hc.out<uint64_t>("eval_rk", (size_t)n);
+  uint64_t* keys_s = hc.out<uint64_t>("eval_rk_s", (size_t)n);
   // the K picked values, then the NaN count, in one slot (one copy back)
-  double* d_res = sc.get<double>("eval_os_res", kMaxRanks + 1);
-  if (!sc.ok) return fail(H3D_ENOMEM, "order statistics buffers");
+  double* d_res = hc.out<double>("eval_os_res", kMaxRanks + 1);
+  if (int rc = hc.ready("order statistics buffers")) return rc;
   int* d_nan = (int*)(d_res + kMaxRanks);
-  HIP_TRY(hipMemcpyAsync(d_v, values, (size_t)n * 8, hipMemcpyHostToDevice, s));
   {
     ProfScope ps(ctx, "eval_order_stats", n);
     HIP_TRY(hipMemsetAsync(d_nan, 0, 8, s));
@@ -589,7 +568,7 @@ int h3d_order_stats(h3d_ctx* ctx, const double* values, int64_t n, const int64_t
     HIP_TRY(hipGetLastError());
   }
   double h[kMaxRanks + 1];
-  if (int rc = d2h_sync(ctx, h, d_res, sizeof(h), s)) return rc;
+  if (int rc = hc.finish(h, d_res, sizeof(h))) return rc;
   for (int j = 0; j < K; ++j) out[j] = h[j];
   int nan = 0;
   std::memcpy(&nan, &h[kMaxRanks], sizeof(int));
@@ -601,8 +580,7 @@ int h3d_bin_fractions(h3d_ctx* ctx, const double* p, const int64_t* dist, int64_
                       const int64_t* lo, const int64_t* hi, int B, double p_star,
                       int64_t* members, int64_t* below) {
   using namespace h3deval;
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (n < 0 || n > kMaxN) return fail(H3D_EARG, "n=%lld outside [0, 2^31)", (long long)n);
+  if (int rc = check_count(ctx, n)) return rc;
   if (B < 1 || B > kMaxRanges) return fail(H3D_EARG, "B=%d outside [1, %d]", B, kMaxRanges);
   if (!lo || !hi || !members || !below) return fail(H3D_EARG, "null argument");
   for (int b = 0; b < B; ++b) members[b] = below[b] = 0;
@@ -614,15 +592,12 @@ int h3d_bin_fractions(h3d_ctx* ctx, const double* p, const int64_t* dist, int64_
     rg.lo[b] = lo[b];
     rg.hi[b] = hi[b];
   }
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_p = sc.get<double>("eval_in_score", (size_t)n);
-  int64_t* d_dist = sc.get<int64_t>("eval_in_row", (size_t)n);
-  unsigned long long* d_cnt = sc.get<unsigned long long>("eval_bf_cnt", 2 * kMaxRanges);
-  if (!sc.ok) return fail(H3D_ENOMEM, "bin fraction buffers");
-  HIP_TRY(hipMemcpyAsync(d_p, p, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_dist, dist, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_p = hc.in("eval_in_score", p, (size_t)n);
+  int64_t* d_dist = hc.in("eval_in_row", dist, (size_t)n);
+  unsigned long long* d_cnt = hc.out<unsigned long long>("eval_bf_cnt", 2 * kMaxRanges);
+  if (int rc = hc.ready("bin fraction buffers")) return rc;
   {
     ProfScope ps(ctx, "eval_bin_fractions", n);
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * kMaxRanges * 8, s));
@@ -631,7 +606,7 @@ int h3d_bin_fractions(h3d_ctx* ctx, const double* p, const int64_t* dist, int64_
     HIP_TRY(hipGetLastError());
   }
   unsigned long long h[2 * kMaxRanges];
-  if (int rc = d2h_sync(ctx, h, d_cnt, sizeof(h), s)) return rc;
+  if (int rc = hc.finish(h, d_cnt, sizeof(h))) return rc;
   for (int b = 0; b < B; ++b) {
     members[b] = (int64_t)h[b];
     below[b] = (int64_t)h[kMaxRanges + b];

@@ -56,17 +56,6 @@ __device__ inline double block_sum(double v, double* lds) {
   return t;
 }
 
-static __global__ void k_i64_to_i32(const int64_t* __restrict__ in,
-                             int32_t* __restrict__ out, int64_t n,
-                             int* __restrict__ overflow) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = in[i];
-    if (v < 0 || v > 0x7fffffffLL) atomicOr(overflow, 1);
-    out[i] = (int32_t)v;
-  }
-}
-
 static __global__ void k_iota(int32_t* __restrict__ out, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)

@@ -130,31 +130,24 @@ int lrt_host(h3d_ctx* ctx, const int64_t* raw, const double* f, const int32_t* d
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (n == 0) return 0;
   if (!raw || !f || !p || !llr || !mu0 || !mu1) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_f = sc.get<double>("in_f", n * R);
-  int32_t* d_dist = dist ? sc.get<int32_t>("in_dist", n) : nullptr;
-  double* d_out = sc.get<double>("lrt_out", n * (3 + 2 * C));
-  if (!sc.ok) return fail(H3D_ENOMEM, "lrt inputs");
-  int32_t* d_raw = nullptr;
-  int* d_ovf = nullptr;
-  if (int rc = upload_counts(ctx, raw, n * R, &d_raw, &d_ovf)) return rc;
-  HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
-  if (dist) HIP_TRY(hipMemcpyAsync(d_dist, dist, n * 4, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  int32_t* d_raw = hc.counts(raw, n * R, "raw counts must be in [0, 2^31)");
+  double* d_f = hc.in("in_f", f, n * R);
+  int32_t* d_dist = hc.in("in_dist", dist, n);
+  // p | llr | mu0 | mu1 (n, C) | disp (n, C)
+  double* d_out = hc.out<double>("lrt_out", n * (3 + 2 * C));
+  if (int rc = hc.ready("lrt inputs")) return rc;
   double *dp = d_out, *dl = d_out + n, *dm0 = d_out + 2 * n, *dm1 = d_out + 3 * n,
          *dd = d_out + (3 + C) * n;
-  int rc = lrt_run(ctx, d_raw, d_f, d_dist, disp_table, n, R, C, cond_of_rep, D,
-                   refit_mu, dp, dl, dm0, dm1, disp_out ? dd : nullptr, wide);
-  int ovf = 0;
-  if (int orc = counts_ovf_copy(ctx, d_ovf, &ovf)) return orc;
-  HIP_TRY(hipMemcpyAsync(p, dp, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(llr, dl, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(mu0, dm0, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(mu1, dm1, n * C * 8, hipMemcpyDeviceToHost, s));
-  if (disp_out) HIP_TRY(hipMemcpyAsync(disp_out, dd, n * C * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (ovf) return fail(H3D_EINPUT, "raw counts must be in [0, 2^31)");
+  // (a failed lrt_run still sends back what it computed: its code comes last)
+  const int rc = lrt_run(ctx, d_raw, d_f, d_dist, disp_table, n, R, C, cond_of_rep, D,
+                         refit_mu, dp, dl, dm0, dm1, disp_out ? dd : nullptr, wide);
+  hc.back(p, dp, n);
+  hc.back(llr, dl, n);
+  hc.back(mu0, dm0, n);
+  hc.back(mu1, dm1, n * C);
+  hc.back(disp_out, dd, n * C);
+  if (int frc = hc.finish()) return frc;
   return rc;
 }
 

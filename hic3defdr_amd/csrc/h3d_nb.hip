@@ -222,17 +222,24 @@ int alpha_count(int64_t sa_px, int64_t sa_rep, int64_t n, int R, int64_t* count)
   return 0;
 }
 
-int fit_mu_run(h3d_ctx* ctx, const int32_t* d_x, const double* d_b,
-               const double* d_alpha, int64_t sa_px, int64_t sa_rep, int64_t n, int R,
-               double* d_mu, int* flags) {
+// the argument checks of fit_mu (host_bufs: host or device buffers, for the
+// wording): 0 = run it, 1 = nothing to do, < 0 = an error
+int fit_mu_args(h3d_ctx* ctx, int64_t sa_px, int64_t sa_rep, int64_t n, int R, int* flags,
+                int64_t* na, bool have_bufs, bool host_bufs) {
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (flags) *flags = 0;
   if (int rc = check_reps(R)) return rc;
-  int64_t na = 0;
-  if (int rc = alpha_count(sa_px, sa_rep, n, R, &na)) return rc;
+  if (int rc = alpha_count(sa_px, sa_rep, n, R, na)) return rc;
   if (n < 0) return fail(H3D_EARG, "n < 0");
-  if (n == 0) return 0;
-  if (!d_x || !d_b || !d_alpha || !d_mu) return fail(H3D_EARG, "null device buffer");
+  if (n == 0) return 1;
+  if (!have_bufs) return fail(H3D_EARG, host_bufs ? "null buffer" : "null device buffer");
+  return 0;
+}
+
+// fit_mu over device buffers (arguments checked); drains the stream
+int fit_mu_run(h3d_ctx* ctx, const int32_t* d_x, const double* d_b,
+               const double* d_alpha, int64_t sa_px, int64_t sa_rep, int64_t n, int R,
+               double* d_mu, int* flags) {
   HIP_TRY(hipSetDevice(ctx->device));
   Scratch sc{ctx};
   int* d_fl = sc.get<int>("nb_flags", 1);
@@ -251,15 +258,20 @@ int fit_mu_run(h3d_ctx* ctx, const int32_t* d_x, const double* d_b,
   return read_flags(ctx, d_fl, flags);
 }
 
-int equalize_run(h3d_ctx* ctx, const int32_t* d_x, const double* d_f, double alpha,
-                 const double* d_alpha_px, int64_t n, int R, double* d_pseudo,
-                 double* d_mu_hat, int* flags) {
+// the same two for equalize
+int equalize_args(h3d_ctx* ctx, int64_t n, int R, int* flags, bool have_bufs, bool host_bufs) {
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (flags) *flags = 0;
   if (int rc = check_reps(R)) return rc;
   if (n < 0) return fail(H3D_EARG, "n < 0");
-  if (n == 0) return 0;
-  if (!d_x || !d_f || !d_pseudo) return fail(H3D_EARG, "null device buffer");
+  if (n == 0) return 1;
+  if (!have_bufs) return fail(H3D_EARG, host_bufs ? "null buffer" : "null device buffer");
+  return 0;
+}
+
+int equalize_run(h3d_ctx* ctx, const int32_t* d_x, const double* d_f, double alpha,
+                 const double* d_alpha_px, int64_t n, int R, double* d_pseudo,
+                 double* d_mu_hat, int* flags) {
   HIP_TRY(hipSetDevice(ctx->device));
   Scratch sc{ctx};
   int* d_fl = sc.get<int>("nb_flags", 1);
@@ -286,6 +298,10 @@ int h3d_nb_fit_mu_dev(h3d_ctx* ctx, const int32_t* d_x, const double* d_b,
                       const double* d_alpha, int64_t alpha_px_stride,
                       int64_t alpha_rep_stride, int64_t n, int R, double* d_mu,
                       int* flags) {
+  int64_t na = 0;
+  if (int rc = fit_mu_args(ctx, alpha_px_stride, alpha_rep_stride, n, R, flags, &na,
+                           d_x && d_b && d_alpha && d_mu, false))
+    return rc < 0 ? rc : 0;
   return fit_mu_run(ctx, d_x, d_b, d_alpha, alpha_px_stride, alpha_rep_stride, n, R,
                     d_mu, flags);
 }
@@ -293,78 +309,47 @@ int h3d_nb_fit_mu_dev(h3d_ctx* ctx, const int32_t* d_x, const double* d_b,
 int h3d_nb_fit_mu(h3d_ctx* ctx, const int64_t* x, const double* b, const double* alpha,
                   int64_t alpha_px_stride, int64_t alpha_rep_stride, int64_t n, int R,
                   double* mu, int* flags) {
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (flags) *flags = 0;
-  if (int rc = check_reps(R)) return rc;
   int64_t na = 0;
-  if (int rc = alpha_count(alpha_px_stride, alpha_rep_stride, n, R, &na)) return rc;
-  if (n < 0) return fail(H3D_EARG, "n < 0");
-  if (n == 0) return 0;
-  if (!x || !b || !alpha || !mu) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_b = sc.get<double>("in_f", n * R);
-  double* d_a = sc.get<double>("nb_alpha", na);
-  double* d_mu = sc.get<double>("nb_out", n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "nb_fit_mu buffers");
-  int32_t* d_x = nullptr;
-  int* d_ovf = nullptr;
-  if (int rc = upload_counts(ctx, x, n * R, &d_x, &d_ovf)) return rc;
-  HIP_TRY(hipMemcpyAsync(d_b, b, n * R * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_a, alpha, na * 8, hipMemcpyHostToDevice, s));
-  int ovf = 0;
-  if (int rc = counts_ovf_copy(ctx, d_ovf, &ovf)) return rc;
+  if (int rc = fit_mu_args(ctx, alpha_px_stride, alpha_rep_stride, n, R, flags, &na,
+                           x && b && alpha && mu, true))
+    return rc < 0 ? rc : 0;
+  HostCall hc(ctx);
+  int32_t* d_x = hc.counts(x, n * R, "counts must be in [0, 2^31)");
+  double* d_b = hc.in("in_f", b, n * R);
+  double* d_a = hc.in("nb_alpha", alpha, na);
+  double* d_mu = hc.out<double>("nb_out", n);
+  if (int rc = hc.ready("nb_fit_mu buffers")) return rc;
   if (int rc = fit_mu_run(ctx, d_x, d_b, d_a, alpha_px_stride, alpha_rep_stride, n, R,
-                          d_mu, flags)) {
-    (void)hipStreamSynchronize(s);  // the copy into ovf
+                          d_mu, flags))
     return rc;
-  }
-  if (ovf) return fail(H3D_EINPUT, "counts must be in [0, 2^31)");
-  HIP_TRY(hipMemcpyAsync(mu, d_mu, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(mu, d_mu, n);
+  return hc.finish();
 }
 
 int h3d_nb_equalize_dev(h3d_ctx* ctx, const int32_t* d_x, const double* d_f,
                         double alpha, const double* d_alpha_px, int64_t n, int R,
                         double* d_pseudo, double* d_mu_hat, int* flags) {
+  if (int rc = equalize_args(ctx, n, R, flags, d_x && d_f && d_pseudo, false))
+    return rc < 0 ? rc : 0;
   return equalize_run(ctx, d_x, d_f, alpha, d_alpha_px, n, R, d_pseudo, d_mu_hat, flags);
 }
 
 int h3d_nb_equalize(h3d_ctx* ctx, const int64_t* x, const double* f, double alpha,
                     const double* alpha_px, int64_t n, int R, double* pseudo,
                     double* mu_hat, int* flags) {
-  if (!ctx) return fail(H3D_EARG, "null ctx");
-  if (flags) *flags = 0;
-  if (int rc = check_reps(R)) return rc;
-  if (n < 0) return fail(H3D_EARG, "n < 0");
-  if (n == 0) return 0;
-  if (!x || !f || !pseudo) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_f = sc.get<double>("in_f", n * R);
-  double* d_a = alpha_px ? sc.get<double>("nb_alpha", n) : nullptr;
-  double* d_out = sc.get<double>("nb_out", n * R + n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "nb_equalize buffers");
-  int32_t* d_x = nullptr;
-  int* d_ovf = nullptr;
-  if (int rc = upload_counts(ctx, x, n * R, &d_x, &d_ovf)) return rc;
-  HIP_TRY(hipMemcpyAsync(d_f, f, n * R * 8, hipMemcpyHostToDevice, s));
-  if (alpha_px) HIP_TRY(hipMemcpyAsync(d_a, alpha_px, n * 8, hipMemcpyHostToDevice, s));
-  int ovf = 0;
-  if (int rc = counts_ovf_copy(ctx, d_ovf, &ovf)) return rc;
+  if (int rc = equalize_args(ctx, n, R, flags, x && f && pseudo, true))
+    return rc < 0 ? rc : 0;
+  HostCall hc(ctx);
+  int32_t* d_x = hc.counts(x, n * R, "counts must be in [0, 2^31)");
+  double* d_f = hc.in("in_f", f, n * R);
+  double* d_a = hc.in("nb_alpha", alpha_px, n);
+  double* d_out = hc.out<double>("nb_out", n * R + n);  // pseudo | mu_hat
+  if (int rc = hc.ready("nb_equalize buffers")) return rc;
   double* d_mu = mu_hat ? d_out + n * R : nullptr;
-  if (int rc = equalize_run(ctx, d_x, d_f, alpha, d_a, n, R, d_out, d_mu, flags)) {
-    (void)hipStreamSynchronize(s);  // the copy into ovf
-    return rc;
-  }
-  if (ovf) return fail(H3D_EINPUT, "counts must be in [0, 2^31)");
-  HIP_TRY(hipMemcpyAsync(pseudo, d_out, n * R * 8, hipMemcpyDeviceToHost, s));
-  if (mu_hat) HIP_TRY(hipMemcpyAsync(mu_hat, d_mu, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  if (int rc = equalize_run(ctx, d_x, d_f, alpha, d_a, n, R, d_out, d_mu, flags)) return rc;
+  hc.back(pseudo, d_out, n * R);
+  hc.back(mu_hat, d_mu, n);
+  return hc.finish();
 }
 
 int h3d_nb_quantile_map(h3d_ctx* ctx, const double* x, double* mu_in, double* mu_out,
@@ -373,29 +358,27 @@ int h3d_nb_quantile_map(h3d_ctx* ctx, const double* x, double* mu_in, double* mu
   if (n < 0) return fail(H3D_EARG, "n < 0");
   if (n == 0) return 0;
   if (!x || !mu_in || !mu_out || !out) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
+  HostCall hc(ctx);
   // x | mu_in | mu_out | out (| alpha)
-  double* d = sc.get<double>("nb_out", n * (alpha_el ? 5 : 4));
-  if (!sc.ok) return fail(H3D_ENOMEM, "nb_quantile_map buffers");
+  double* d = hc.out<double>("nb_out", n * (alpha_el ? 5 : 4));
+  if (int rc = hc.ready("nb_quantile_map buffers")) return rc;
   double *d_x = d, *d_mi = d + n, *d_mo = d + 2 * n, *d_out = d + 3 * n;
   double* d_a = alpha_el ? d + 4 * n : nullptr;
-  HIP_TRY(hipMemcpyAsync(d_x, x, n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_mi, mu_in, n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_mo, mu_out, n * 8, hipMemcpyHostToDevice, s));
-  if (alpha_el) HIP_TRY(hipMemcpyAsync(d_a, alpha_el, n * 8, hipMemcpyHostToDevice, s));
+  hc.up(d_x, x, n);
+  hc.up(d_mi, mu_in, n);
+  hc.up(d_mo, mu_out, n);
+  hc.up(d_a, alpha_el, n);
   {
     ProfScope ps(ctx, "nb_quantile_map", n);
     hipLaunchKernelGGL(k_nb_quantile_map, dim3(grid_for(ctx, n, 16)), dim3(kBlock), 0, s,
                        d_x, d_mi, d_mo, alpha, d_a, n, d_out);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(mu_in, d_mi, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(mu_out, d_mo, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(out, d_out, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(mu_in, d_mi, n);
+  hc.back(mu_out, d_mo, n);
+  hc.back(out, d_out, n);
+  return hc.finish();
 }
 
 int h3d_nb_logpmf(h3d_ctx* ctx, const double* k, const double* m, const double* phi,
@@ -404,23 +387,20 @@ int h3d_nb_logpmf(h3d_ctx* ctx, const double* k, const double* m, const double* 
   if (n < 0) return fail(H3D_EARG, "n < 0");
   if (n == 0) return 0;
   if (!k || !m || !phi || !out) return fail(H3D_EARG, "null buffer");
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d = sc.get<double>("nb_out", n * 4);
-  if (!sc.ok) return fail(H3D_ENOMEM, "nb_logpmf buffers");
-  HIP_TRY(hipMemcpyAsync(d, k, n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + n, m, n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + 2 * n, phi, n * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d = hc.out<double>("nb_out", n * 4);  // k | m | phi | out
+  if (int rc = hc.ready("nb_logpmf buffers")) return rc;
+  hc.up(d, k, n);
+  hc.up(d + n, m, n);
+  hc.up(d + 2 * n, phi, n);
   {
     ProfScope ps(ctx, "nb_logpmf", n);
-    hipLaunchKernelGGL(k_nb_logpmf, dim3(grid_for(ctx, n, 16)), dim3(kBlock), 0, s, d,
-                       d + n, d + 2 * n, n, d + 3 * n);
+    hipLaunchKernelGGL(k_nb_logpmf, dim3(grid_for(ctx, n, 16)), dim3(kBlock), 0, ctx->stream,
+                       d, d + n, d + 2 * n, n, d + 3 * n);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, d + 3 * n, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(out, d + 3 * n, n);
+  return hc.finish();
 }
 
 }  // extern "C"

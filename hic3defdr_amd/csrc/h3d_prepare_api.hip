@@ -223,10 +223,10 @@ int h3d_union_fill_dev(h3d_ctx* ctx, int32_t* row, int32_t* col, int64_t* raw,
   // fetches it in the background, analysis/d2h.py)
   if (!row || !col || (!raw && !d_raw_out) || (!balanced && !d_bal_out))
     return fail(H3D_EARG, "null output");
-  HIP_TRY(hipSetDevice(ctx->device));
+  HostCall hc(ctx);
+  Scratch& sc = hc.sc;
   hipStream_t s = ctx->stream;
   const int R = P.R;
-  Scratch sc{ctx};
   int32_t* d_row = sc.get<int32_t>("u_out_row", n_px);
   int32_t* d_col = sc.get<int32_t>("u_out_col", n_px);
   int64_t* d_raw = sc.get<int64_t>("u_out_raw", n_px * R);
@@ -234,7 +234,7 @@ int h3d_union_fill_dev(h3d_ctx* ctx, int32_t* row, int32_t* col, int64_t* raw,
   // (h3d_union_count's flags, by their slot)
   int32_t* keep = sc.get<int32_t>("u_keep", std::max<int64_t>(P.n_runs, 1));
   int* d_ovf = sc.get<int>("ovf", 1);
-  if (!sc.ok) return fail(H3D_ENOMEM, "union out");
+  if (int rc = hc.ready("union out")) return rc;
   hipLaunchKernelGGL(k_union_fill, dim3(grid_for(ctx, P.n_runs)), dim3(kBlock), 0, s,
                      P.keys_sorted, P.ent_sorted, P.run_start, keep, P.px_of_run,
                      P.n_runs, P.n_entries, P.ent_rep, P.ent_val, R, P.n_bins, P.bias,
@@ -245,19 +245,16 @@ int h3d_union_fill_dev(h3d_ctx* ctx, int32_t* row, int32_t* col, int64_t* raw,
   if (d_col_out) HIP_TRY(hipMemcpyAsync(d_col_out, d_col, n_px * 4, hipMemcpyDeviceToDevice, s));
   if (d_bal_out)
     HIP_TRY(hipMemcpyAsync(d_bal_out, d_bal, n_px * R * 8, hipMemcpyDeviceToDevice, s));
-  int ovf = 0;
-  if (d_raw_out) {
+  if (d_raw_out) {  // finish() reads the overflow word
     if (int rc = counts_to_i32(ctx, d_raw, d_raw_out, n_px * R, d_ovf)) return rc;
-    if (int rc = counts_ovf_copy(ctx, d_ovf, &ovf)) return rc;
+    hc.d_ovf = d_ovf;
+    hc.ovf_msg = "raw counts must be in [0, 2^31) for the device copy";
   }
-  HIP_TRY(hipMemcpyAsync(row, d_row, n_px * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(col, d_col, n_px * 4, hipMemcpyDeviceToHost, s));
-  if (raw) HIP_TRY(hipMemcpyAsync(raw, d_raw, n_px * R * 8, hipMemcpyDeviceToHost, s));
-  if (balanced)
-    HIP_TRY(hipMemcpyAsync(balanced, d_bal, n_px * R * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (ovf) return fail(H3D_EINPUT, "raw counts must be in [0, 2^31) for the device copy");
-  return 0;
+  hc.back(row, d_row, n_px);
+  hc.back(col, d_col, n_px);
+  hc.back(raw, d_raw, n_px * R);
+  hc.back(balanced, d_bal, n_px * R);
+  return hc.finish();
 }
 
 // d_disp_idx (n) 0/1 -> the chromosome's disp pixels (k_disp_pixels)
@@ -355,19 +352,17 @@ int h3d_scale_disp_dev(h3d_ctx* ctx, const double* d_balanced, const double* d_s
   a.C = C;
   a.mean_thresh = mean_thresh;
   a.dist_min = dist_thresh_min;
-  HIP_TRY(hipSetDevice(ctx->device));
+  HostCall hc(ctx);  // (device inputs: only the two results are staged)
   hipStream_t s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_scaled = d_scaled_out ? d_scaled_out : sc.get<double>("sd_scaled", (size_t)n * R);
-  uint8_t* d_flag = d_flag_out ? d_flag_out : sc.get<uint8_t>("sd_flag", (size_t)n);
-  if (!sc.ok) return fail(H3D_ENOMEM, "scale / disp scratch");
+  double* d_scaled = d_scaled_out ? d_scaled_out : hc.out<double>("sd_scaled", (size_t)n * R);
+  uint8_t* d_flag = d_flag_out ? d_flag_out : hc.out<uint8_t>("sd_flag", (size_t)n);
+  if (int rc = hc.ready("scale / disp scratch")) return rc;
   hipLaunchKernelGGL(k_scale_disp, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_balanced,
                      d_sf, sf_per_rep, d_row, d_col, n, R, a, d_scaled, d_flag);
   HIP_TRY(hipGetLastError());
-  if (scaled_out)
-    HIP_TRY(hipMemcpyAsync(scaled_out, d_scaled, (size_t)n * R * 8, hipMemcpyDeviceToHost, s));
+  hc.back(scaled_out, d_scaled, (size_t)n * R);
   // (the flags through the pinned landing zone: see h2d_pinned)
-  return d2h_sync(ctx, flag_out, d_flag, (size_t)n, s);
+  return hc.finish(flag_out, d_flag, (size_t)n);
 }
 
 int h3d_table_gather_dev(h3d_ctx* ctx, const double* d_tables, int D, int C,
@@ -401,6 +396,7 @@ struct SfCall {
   int R, norm, n_bins;
   double *sf_out, *d_sf_out;
   hipStream_t s = nullptr;
+  HostCall* hc = nullptr;  // stages balanced (from the host) and sf_out
   // per-distance factors (n, R), else one set (R,); by median of ratios, else
   // by simple scaling
   bool conditional = false, mor = false;
@@ -468,17 +464,15 @@ int sf_order_and_bins(SfCall& c) {
   const int R = c.R;
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = c.s = ctx->stream;
-  Scratch sc{ctx};
-  double* d_bal = c.d_balanced ? nullptr : sc.get<double>("sf_bal", n * R);
+  Scratch& sc = c.hc->sc;
+  double* d_bal = c.hc->in("sf_bal", c.balanced, n * R);
   c.d_dist = sc.get<int32_t>("sf_dist", n);
   c.d_dist_s = sc.get<int32_t>("sf_dist_s", n);
   c.d_idx = sc.get<int32_t>("sf_idx", n);
   c.d_perm = sc.get<int32_t>("sf_perm", n);
   c.d_bin = sc.get<int32_t>("sf_bin", n);
   c.d_sf = sc.get<double>("sf_out", n * R);
-  if (!sc.ok) return fail(H3D_ENOMEM, "size factor scratch");
-  if (!c.d_balanced)
-    HIP_TRY(hipMemcpyAsync(d_bal, c.balanced, n * R * 8, hipMemcpyHostToDevice, s));
+  if (int rc = c.hc->ready("size factor scratch")) return rc;
   c.bal = c.d_balanced ? c.d_balanced : d_bal;
   hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_idx, n);
   if (!c.conditional) {
@@ -611,6 +605,7 @@ int sf_pixel_factors(SfCall& c) {
   hipStream_t s = c.s;
   const int64_t n = c.n;
   const int R = c.R, nb = c.nb;
+  std::vector<double> xp, yp;  // (alive until the call's last synchronisation)
   if (c.n_bins > 0) {
     hipLaunchKernelGGL(k_bin_dist_sum, dim3(nb), dim3(256), 0, s, c.d_dist_s, c.d_bstart, nb,
                        c.d_dpb);
@@ -618,7 +613,6 @@ int sf_pixel_factors(SfCall& c) {
     HIP_TRY(hipMemcpyAsync(dpb.data(), c.d_dpb, nb * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // np.unique(bins): only non-empty bins take part in the interpolation
-    std::vector<double> xp, yp;
     for (int b = 0; b < nb; ++b)
       if (c.bstart[b + 1] > c.bstart[b]) {
         xp.push_back(dpb[b]);
@@ -630,20 +624,19 @@ int sf_pixel_factors(SfCall& c) {
     double* d_xp = sc.get<double>("sf_xp", m);
     double* d_yp = sc.get<double>("sf_yp", (size_t)m * R);
     if (!sc.ok) return fail(H3D_ENOMEM, "interp");
-    HIP_TRY(hipMemcpyAsync(d_xp, xp.data(), m * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_yp, yp.data(), (size_t)m * R * 8, hipMemcpyHostToDevice, s));
+    c.hc->up(d_xp, xp.data(), (size_t)m);
+    c.hc->up(d_yp, yp.data(), (size_t)m * R);
     hipLaunchKernelGGL(k_sf_interp, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_dist, n, R,
                        d_xp, d_yp, m, c.d_sf);
   } else {
-    HIP_TRY(hipMemcpyAsync(c.d_spb, c.spb.data(), (size_t)nb * R * 8, hipMemcpyHostToDevice, s));
+    c.hc->up(c.d_spb, c.spb.data(), (size_t)nb * R);
     hipLaunchKernelGGL(k_sf_exact, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_perm, c.d_bin,
                        n, R, c.d_spb, c.d_sf);
   }
   if (c.d_sf_out)
     HIP_TRY(hipMemcpyAsync(c.d_sf_out, c.d_sf, n * R * 8, hipMemcpyDeviceToDevice, s));
-  if (c.sf_out) HIP_TRY(hipMemcpyAsync(c.sf_out, c.d_sf, n * R * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  c.hc->back(c.sf_out, c.d_sf, (size_t)n * R);
+  return c.hc->finish();
 }
 
 int size_factors_impl(h3d_ctx* ctx, const double* balanced, const double* d_balanced,
@@ -653,6 +646,8 @@ int size_factors_impl(h3d_ctx* ctx, const double* balanced, const double* d_bala
   bool done = false;
   if (int rc = sf_check_and_trivial(c, &done)) return rc;
   if (done) return 0;
+  HostCall hc(ctx);
+  c.hc = &hc;
   if (int rc = sf_order_and_bins(c)) return rc;
   if (int rc = c.mor ? sf_bin_factors_mor(c) : sf_bin_factors_scaling(c)) return rc;
   if (c.conditional) return sf_pixel_factors(c);

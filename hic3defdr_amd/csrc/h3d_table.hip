@@ -739,13 +739,8 @@ int h3d_disp_tables_dev(h3d_ctx* ctx, const double* d_disp_per_dist, int D, int 
     return 0;
   }
   ctx->tab_pending.on_host = 0;
-  int& attr = ctx->resident[(const void*)k_disp_table];
-  if (!attr) {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_disp_table,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes(kMaxD)));
-    attr = 1;
-  }
+  if (int rc = allow_dynamic_lds(ctx, (const void*)k_disp_table, (int)lds_bytes(kMaxD)))
+    return rc;
   {
     ProfScope ps(ctx, "disp_table", D);
     unsigned long long* d_stamps = nullptr;

@@ -159,10 +159,13 @@ __global__ __launch_bounds__(kBlock) void k_stack_final(const int64_t* __restric
   }
 }
 
-// the argument checks shared by the two gather entry points; *n_cells = the
-// cells of one data column (W * h * w)
-int check_gather(const void* ctx, int ld, int n_rows, int n_cols, const int32_t* cols, int K,
-                 int64_t W, int h, int w, int64_t nnz, int64_t* n_cells) {
+// the argument checks shared by the two gather entry points (host or device
+// buffers); *n_cells = the cells of one data column (W * h * w). 0 = run it,
+// 1 = no windows, < 0 = an error
+int check_gather(const void* ctx, const void* indptr, const void* row, const void* indices,
+                 const void* data, int ld, int n_rows, int n_cols, const int32_t* cols, int K,
+                 const void* origins, int64_t W, int h, int w, int64_t nnz, const void* out,
+                 int64_t* n_cells) {
   if (!ctx) return fail(H3D_EARG, "null ctx");
   if (h < 1 || w < 1) return fail(H3D_EARG, "window shape %d x %d: h and w must be >= 1", h, w);
   if (K < 1) return fail(H3D_EARG, "K=%d: at least one data column", K);
@@ -182,6 +185,10 @@ int check_gather(const void* ctx, int ld, int n_rows, int n_cols, const int32_t*
     return fail(H3D_EARG, "K * W * h * w = %d * %lld * %d * %d is not below 2^31", K,
                 (long long)W, h, w);
   *n_cells = W * per;
+  if (W == 0) return 1;
+  if (!origins || !out) return fail(H3D_EARG, "null origins / output");
+  if (!indptr && !row && nnz > 0) return fail(H3D_EARG, "neither indptr nor row given");
+  if (nnz > 0 && (!indices || !data)) return fail(H3D_EARG, "null indices / data");
   return 0;
 }
 
@@ -225,11 +232,9 @@ int h3d_window_gather_dev(h3d_ctx* ctx, const int64_t* d_indptr, const int32_t* 
                           int mean, double fill, double* d_out) {
   using namespace h3dviews;
   int64_t n_cells = 0;
-  if (int rc = check_gather(ctx, ld, n_rows, n_cols, cols, K, W, h, w, nnz, &n_cells)) return rc;
-  if (W == 0) return 0;
-  if (!d_origins || !d_out) return fail(H3D_EARG, "null origins / output");
-  if (!d_indptr && !d_row && nnz > 0) return fail(H3D_EARG, "neither indptr nor row given");
-  if (nnz > 0 && (!d_indices || !d_data)) return fail(H3D_EARG, "null indices / data");
+  if (int rc = check_gather(ctx, d_indptr, d_row, d_indices, d_data, ld, n_rows, n_cols, cols, K,
+                            d_origins, W, h, w, nnz, d_out, &n_cells))
+    return rc < 0 ? rc : 0;
   HIP_TRY(hipSetDevice(ctx->device));
   if (int rc = launch_gather(ctx, d_indptr, d_row, d_indices, d_data, nnz, ld, n_rows, n_cols,
                              cols, K, d_origins, n_cells, h, w, symmetrize, mean, fill, d_out))
@@ -245,11 +250,9 @@ int h3d_window_gather(h3d_ctx* ctx, const int64_t* indptr, const int32_t* row,
                       int mean, double fill, double* out) {
   using namespace h3dviews;
   int64_t n_cells = 0;
-  if (int rc = check_gather(ctx, ld, n_rows, n_cols, cols, K, W, h, w, nnz, &n_cells)) return rc;
-  if (W == 0) return 0;
-  if (!origins || !out) return fail(H3D_EARG, "null origins / output");
-  if (!indptr && !row && nnz > 0) return fail(H3D_EARG, "neither indptr nor row given");
-  if (nnz > 0 && (!indices || !data)) return fail(H3D_EARG, "null indices / data");
+  if (int rc = check_gather(ctx, indptr, row, indices, data, ld, n_rows, n_cols, cols, K,
+                            origins, W, h, w, nnz, out, &n_cells))
+    return rc < 0 ? rc : 0;
   if (indptr) {  // a caller's row pointers must stay inside indices
     if (indptr[0] < 0 || indptr[n_rows] > nnz)
       return fail(H3D_EARG, "indptr spans [%lld, %lld], nnz = %lld", (long long)indptr[0],
@@ -257,31 +260,23 @@ int h3d_window_gather(h3d_ctx* ctx, const int64_t* indptr, const int32_t* row,
     for (int r = 0; r < n_rows; ++r)
       if (indptr[r] > indptr[r + 1]) return fail(H3D_EARG, "indptr decreases at row %d", r);
   }
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
   const int64_t n_out = mean ? n_cells : (int64_t)K * n_cells;
-  Scratch sc{ctx};
-  int64_t* d_indptr = indptr ? sc.get<int64_t>("views_indptr", (size_t)n_rows + 1) : nullptr;
-  int32_t* d_row = indptr ? nullptr : sc.get<int32_t>("views_row", (size_t)nnz + 1);
-  int32_t* d_indices = sc.get<int32_t>("views_indices", (size_t)nnz + 1);
-  double* d_data = sc.get<double>("views_data", (size_t)nnz * ld + 1);
-  int32_t* d_origins = sc.get<int32_t>("views_origins", (size_t)W * 2);
-  double* d_out = sc.get<double>("views_out", (size_t)n_out);
-  if (!sc.ok) return fail(H3D_ENOMEM, "window gather buffers");
-  if (indptr)
-    HIP_TRY(hipMemcpyAsync(d_indptr, indptr, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, s));
-  if (nnz > 0) {
-    if (!indptr) HIP_TRY(hipMemcpyAsync(d_row, row, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_data, data, (size_t)nnz * ld * 8, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d_origins, origins, (size_t)W * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  int64_t* d_indptr = hc.in("views_indptr", indptr, (size_t)n_rows + 1);
+  int32_t* d_row = indptr ? nullptr : hc.out<int32_t>("views_row", (size_t)nnz + 1);
+  hc.up(d_row, row, (size_t)nnz);
+  int32_t* d_indices = hc.out<int32_t>("views_indices", (size_t)nnz + 1);
+  hc.up(d_indices, indices, (size_t)nnz);
+  double* d_data = hc.out<double>("views_data", (size_t)nnz * ld + 1);
+  hc.up(d_data, data, (size_t)nnz * ld);
+  int32_t* d_origins = hc.in("views_origins", origins, (size_t)W * 2);
+  double* d_out = hc.out<double>("views_out", (size_t)n_out);
+  if (int rc = hc.ready("window gather buffers")) return rc;
   if (int rc = launch_gather(ctx, d_indptr, d_row, d_indices, d_data, nnz, ld, n_rows, n_cols,
                              cols, K, d_origins, n_cells, h, w, symmetrize, mean, fill, d_out))
     return rc;
-  HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(out, d_out, (size_t)n_out);
+  return hc.finish();
 }
 
 int h3d_stack_aggregate(h3d_ctx* ctx, const double* stack, int64_t W, int h, int w,
@@ -302,17 +297,15 @@ int h3d_stack_aggregate(h3d_ctx* ctx, const double* stack, int64_t W, int h, int
     return 0;
   }
   if (!stack) return fail(H3D_EARG, "null stack");
-  HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int64_t n_chunks = (W + kAggChunk - 1) / kAggChunk;
-  Scratch sc{ctx};
-  double* d_stack = sc.get<double>("views_out", (size_t)W * cells);
-  int64_t* d_pcount = sc.get<int64_t>("views_pcount", (size_t)n_chunks * cells);
-  double* d_psum = sc.get<double>("views_psum", (size_t)n_chunks * cells);
-  int64_t* d_count = sc.get<int64_t>("views_count", (size_t)cells);
-  double* d_sum = sc.get<double>("views_sum", (size_t)cells);
-  if (!sc.ok) return fail(H3D_ENOMEM, "stack aggregate buffers");
-  HIP_TRY(hipMemcpyAsync(d_stack, stack, (size_t)W * cells * 8, hipMemcpyHostToDevice, s));
+  HostCall hc(ctx);
+  double* d_stack = hc.in("views_out", stack, (size_t)W * cells);
+  int64_t* d_pcount = hc.out<int64_t>("views_pcount", (size_t)n_chunks * cells);
+  double* d_psum = hc.out<double>("views_psum", (size_t)n_chunks * cells);
+  int64_t* d_count = hc.out<int64_t>("views_count", (size_t)cells);
+  double* d_sum = hc.out<double>("views_sum", (size_t)cells);
+  if (int rc = hc.ready("stack aggregate buffers")) return rc;
   {
     ProfScope ps(ctx, "stack_aggregate", W * cells);
     hipLaunchKernelGGL(k_stack_partial, dim3(grid_for(ctx, n_chunks * cells)), dim3(kBlock), 0,
@@ -321,10 +314,9 @@ int h3d_stack_aggregate(h3d_ctx* ctx, const double* stack, int64_t W, int h, int
                        d_psum, cells, n_chunks, d_count, d_sum);
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(count, d_count, (size_t)cells * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(sum, d_sum, (size_t)cells * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  hc.back(count, d_count, (size_t)cells);
+  hc.back(sum, d_sum, (size_t)cells);
+  return hc.finish();
 }
 
 }  // extern "C"
