@@ -11,6 +11,14 @@
                           FMA-chain kernel and a 16 B/lane copy); measurement
                           only, never loaded by the product.
 
+``libh3d.so`` is linked without relocatable device code: every ``.hip`` unit
+carries its own device code object, and a kernel that two units compile is
+shipped twice. So each kernel has one home (tests/test_device_units.py reads
+the objects under ``lib/obj`` and holds the build to it): hipcub / rocprim
+are instantiated by the ``h3d_cub_*.hip`` units alone, behind the plain
+declarations of ``csrc/h3d_cub.h``, and a header that defines a non-template
+``__global__`` function is included by one unit.
+
 All land in ``hic3defdr_amd/lib/`` so they travel to the GPU box with the
 repo snapshot (they are git-ignored, not gpurun-ignored).
 
@@ -43,6 +51,8 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
                ('h3d_nb.hip', 'hipcc'), ('h3d_diag.hip', 'hipcc'),
                ('h3d_eval.hip', 'hipcc'), ('h3d_ctx.hip', 'hipcc'),
+               ('h3d_cub_sort_idx.hip', 'hipcc'), ('h3d_cub_sort_int.hip', 'hipcc'),
+               ('h3d_cub_sort_f64.hip', 'hipcc'), ('h3d_cub_scan.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]
 # concurrent compiles (each hipcc TU is single-threaded; the box sets
 # MAX_JOBS=16, this container has 8 CPUs)

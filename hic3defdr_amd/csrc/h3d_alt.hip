@@ -10,7 +10,7 @@
 // Global3DeFDR needs no kernel of its own: its single qcml per condition over
 // the loop pixels is h3d_disp_per_dist with one distance segment.
 //
-// Layout as the main LRT (h3d_kernels.h): pixels in the reference order,
+// Layout as the main LRT (h3d_lrt_kernel.h): pixels in the reference order,
 // replicate-minor rows; one lane per pixel. Both kernels are light (a few
 // logs / lgammas per replicate), i.e. HBM-bound: 12R + 16C + 16 B/px
 // (Poisson: raw int32 + f in; p, llr, mu0, mu1 out) and 8R + 8C B/px (MME).

@@ -3,7 +3,6 @@
 // in h3d_lrt.hip, prepare_data's in h3d_prepare_api.hip (separate TUs,
 // compiled in parallel).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -20,6 +19,7 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_cub.h"
 #include "h3d_errors.h"
 #include "h3d_host.h"
 #include "h3d_kernels.h"
@@ -418,8 +418,8 @@ int radix_sort_pairs(h3d_ctx* ctx, const char* tmp_slot, hipStream_t s, const K*
                      K* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n,
                      int begin_bit, int end_bit) {
   return cub_call(ctx, tmp_slot, [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out,
-                                              (int)n, begin_bit, end_bit, s);
+    return sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, begin_bit, end_bit,
+                      s);
   });
 }
 
@@ -429,9 +429,8 @@ template <typename K>
 int radix_sort_temp_bytes(int64_t n, int begin_bit, int end_bit, size_t* bytes) {
   return cub_bytes(
       [&](void* tmp, size_t& b) {
-        return hipcub::DeviceRadixSort::SortPairs(tmp, b, (const K*)nullptr, (K*)nullptr,
-                                                  (const int32_t*)nullptr, (int32_t*)nullptr,
-                                                  (int)n, begin_bit, end_bit, (hipStream_t) nullptr);
+        return sort_pairs(tmp, b, (const K*)nullptr, (K*)nullptr, (const int32_t*)nullptr,
+                          (int32_t*)nullptr, (int)n, begin_bit, end_bit, (hipStream_t) nullptr);
       },
       bytes);
 }
@@ -641,7 +640,7 @@ int sort_and_gather(DispCall& c) {
   c.pd = sc.get<double>("pd", n * R);
   c.d_seg = sc.get<int64_t>("seg_start", D + 1);
   if (!sc.ok) return fail(H3D_ENOMEM, "device allocation failed (n=%lld)", (long long)n);
-  hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, c.s, idx_in, n);
+  launch_iota(ctx, c.s, idx_in, n);
   int end_bit = 1;
   while ((1 << end_bit) <= D) ++end_bit;
   if (int rc = end_bit <= 16 ? sort_by_condition<uint32_t>(c, end_bit, idx_in, idx_out)

@@ -25,7 +25,6 @@
 //    per-block partial -> one fixed-order pass over the partials, which each
 //    consumer block repeats for itself, so a rerun gives the same bits.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -35,6 +34,7 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_cub.h"
 #include "h3d_errors.h"
 
 #pragma clang fp contract(off)
@@ -603,7 +603,7 @@ int upload_and_filter(Setup& u, const int64_t* indptr, const int32_t* indices,
 int scan_i32(h3d_ctx* ctx, const int32_t* in, int32_t* out, int64_t count) {
   hipStream_t s = ctx->stream;
   return cub_call(ctx, "kr_cub", [&](void* tmp, size_t& tb) {
-    return hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)count, s);
+    return exclusive_sum(tmp, tb, in, out, (int)count, s);
   });
 }
 
@@ -837,8 +837,7 @@ int h3d_kr_balance(h3d_ctx* ctx, const int64_t* indptr, const int32_t* indices,
     if (int rc = scan_i32(ctx, u.d_keep, u.d_pos, nnz + 1)) return rc;
     if (int rc = scan_i32(ctx, d_cntl, d_lowptr, (int64_t)n + 1)) return rc;
     if (int rc = cub_call(ctx, "kr_cub", [&](void* tmp, size_t& tb) {
-          return hipcub::DeviceRadixSort::SortPairs(tmp, tb, d_key, d_skey, d_val, d_sval,
-                                                    (int)nnz, 0, end_bit, s);
+          return sort_pairs(tmp, tb, d_key, d_skey, d_val, d_sval, (int)nnz, 0, end_bit, s);
         }))
       return rc;
     hipLaunchKernelGGL(k_full_rowptr, dim3(grid_for(ctx, (int64_t)n + 1)), dim3(kBlock), 0, s,

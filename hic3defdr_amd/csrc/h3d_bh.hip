@@ -11,12 +11,12 @@
 // division is monotone), so the reverse minimum gives the whole tie the same
 // q whatever order the sort left it in.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <cmath>
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_cub.h"
 #include "h3d_errors.h"
 
 using namespace h3dint;
@@ -65,10 +65,6 @@ __global__ void k_bh_scatter(const double* __restrict__ scanned,
     q[order[j]] = v;
   }
 }
-
-struct MinOp {
-  __device__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
 
 // ---- BH over p-values sharded across ranks (parallel.bh_sharded) ----------
 // Each rank sorts its own p-values (h3d_bh_sort_dev), ships them to the rank
@@ -148,15 +144,15 @@ int h3d_bh_dev(h3d_ctx* ctx, const double* d_p, int64_t n, double* d_q) {
   double* scanned = sc.get<double>("bh_scan", n);
   if (!sc.ok) return fail(H3D_ENOMEM, "bh scratch");
   auto count = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceReduce::Sum(tmp, bytes, fin, d_m, (int)n, s);
+    return reduce_sum(tmp, bytes, fin, d_m, (int)n, s);
   };
   auto sort = [&](void* tmp, size_t& tb) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key_s, idx, idx_s, (int)n, 0, 64, s);
+    return sort_pairs(tmp, tb, key, key_s, idx, idx_s, (int)n, 0, 64, s);
   };
   // min-scan over the first m entries: the count lives on the device, so scan
   // all n -- entries >= m are never read (k_bh_scatter reads m - 1 - j < m)
   auto min_scan = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceScan::InclusiveScan(tmp, bytes, key, scanned, MinOp(), (int)n, s);
+    return inclusive_min(tmp, bytes, key, scanned, (int)n, s);
   };
   // one temp for the three, reserved at the largest before the first runs
   // (growing it between them would put a hipFree, a device synchronisation,
@@ -197,11 +193,10 @@ int h3d_bh_sort_dev(h3d_ctx* ctx, const double* d_p, const int64_t* d_val, int64
   hipLaunchKernelGGL(k_bh_sort_in, dim3(grid), dim3(kBhBlock), 0, s, d_p, d_val, n, key, val,
                      fin);
   auto count = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceReduce::Sum(tmp, bytes, fin, d_m, (int)n, s);
+    return reduce_sum(tmp, bytes, fin, d_m, (int)n, s);
   };
   auto sort = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, d_key_out, val, d_val_out,
-                                              (int)n, 0, 64, s);
+    return sort_pairs(tmp, bytes, key, d_key_out, val, d_val_out, (int)n, 0, 64, s);
   };
   // one temp for both, reserved at the larger before the first runs
   size_t tb = 0, tb2 = 0;
@@ -239,7 +234,7 @@ int h3d_bh_scan_dev(h3d_ctx* ctx, const double* d_ps, int64_t mb, int64_t offset
   hipLaunchKernelGGL(k_bh_ratio_off, dim3(grid), dim3(kBhBlock), 0, s, d_ps, mb, offset, m,
                      rev);
   if (int rc = cub_call(ctx, "cub_tmp_bhs2", [&](void* tmp, size_t& bytes) {
-        return hipcub::DeviceScan::InclusiveScan(tmp, bytes, rev, srev, MinOp(), (int)mb, s);
+        return inclusive_min(tmp, bytes, rev, srev, (int)mb, s);
       }))
     return rc;
   hipLaunchKernelGGL(k_bh_unreverse, dim3(grid), dim3(kBhBlock), 0, s, srev, mb, d_scanned);

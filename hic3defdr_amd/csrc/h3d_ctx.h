@@ -265,8 +265,8 @@ struct HostCall {
   int finish(void* dst, const void* d_src, size_t bytes);
 };
 
-// hipcub's two-phase calls. op(tmp, bytes) is the hipcub call itself
-// (hipError_t(void*, size_t&)): with tmp = nullptr it only reports its temp
+// hipcub's two-phase calls. op(tmp, bytes) is the operation, one of
+// h3d_cub.h's (hipError_t(void*, size_t&)): with tmp = nullptr it only reports its temp
 // size. cub_bytes is that query alone; cub_call queries, takes the temp out
 // of the ctx slot (grow-only: a slot reserved larger beforehand is reused as
 // it is) and runs the operation.
@@ -293,6 +293,8 @@ int cub_call(h3d_ctx* ctx, const char* tmp_slot, Op op) {
 // and HostCall::finish reads the word (H3D_EINPUT).
 int counts_to_i32(h3d_ctx* ctx, const int64_t* d_raw64, int32_t* d_raw, int64_t count,
                   int* d_ovf);
+// out[i] = i for i in [0, n), enqueued on s (k_iota, h3d_ctx.hip)
+void launch_iota(h3d_ctx* ctx, hipStream_t s, int32_t* out, int64_t n);
 hipEvent_t ev_get(h3d_ctx* ctx);
 // host -> device copy of `bytes` through the ctx's pinned bounce buffer,
 // stream-ordered on s (the source may be reused at once)

@@ -31,6 +31,12 @@ static __global__ void k_i64_to_i32(const int64_t* __restrict__ in,
   }
 }
 
+static __global__ void k_iota(int32_t* __restrict__ out, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (int32_t)i;
+}
+
 }  // namespace h3d
 
 namespace h3dint {
@@ -100,6 +106,10 @@ int counts_to_i32(h3d_ctx* ctx, const int64_t* d_raw64, int32_t* d_raw, int64_t 
   hipLaunchKernelGGL(k_i64_to_i32, dim3(grid_for(ctx, count)), dim3(kLaunchBlock), 0, ctx->stream,
                      d_raw64, d_raw, count, d_ovf);
   return 0;
+}
+
+void launch_iota(h3d_ctx* ctx, hipStream_t s, int32_t* out, int64_t n) {
+  hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kLaunchBlock), 0, s, out, n);
 }
 
 int d2h_sync(h3d_ctx* ctx, void* dst, const void* d_src, size_t bytes, hipStream_t s) {

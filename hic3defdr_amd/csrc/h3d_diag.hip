@@ -24,7 +24,6 @@
 // rerun, another grid or another ctx gives the same bits. Counts are integer
 // atomics (exact in any order).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <cmath>
 #include <cstdint>
@@ -33,6 +32,7 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_cub.h"
 #include "h3d_devutil.h"
 #include "h3d_errors.h"
 #include "h3d_model.h"
@@ -176,8 +176,7 @@ int launch_group_sums(h3d_ctx* ctx, const int32_t* d_keys, const double* d_value
     int end_bit = 1;
     while (end_bit < 32 && ((uint32_t)K >> end_bit)) ++end_bit;
     if (int rc = cub_call(ctx, "cub_tmp_diag", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ku, ks, idx, idx_s, (int)n, 0,
-                                                    end_bit, s);
+          return sort_pairs(tmp, bytes, ku, ks, idx, idx_s, (int)n, 0, end_bit, s);
         }))
       return rc;
   }
@@ -405,13 +404,12 @@ int launch_rank_average(h3d_ctx* ctx, const double* d_values, int64_t n, int R, 
     const double* col = d_values + (int64_t)c * n;
     hipLaunchKernelGGL(k_rank_keys, dim3(g), dim3(kBlock), 0, s, col, n, keys, idx, d_flags + c);
     if (int rc = cub_call(ctx, "cub_tmp_diag", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, keys_s, idx, idx_s, (int)n,
-                                                    0, 64, s);
+          return sort_pairs(tmp, bytes, keys, keys_s, idx, idx_s, (int)n, 0, 64, s);
         }))
       return rc;
     hipLaunchKernelGGL(k_rank_heads, dim3(g), dim3(kBlock), 0, s, keys_s, n, head);
     if (int rc = cub_call(ctx, "cub_tmp_diag_s", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceScan::InclusiveSum(tmp, bytes, head, run_of, (int)n, s);
+          return inclusive_sum(tmp, bytes, head, run_of, (int)n, s);
         }))
       return rc;
     hipLaunchKernelGGL(k_rank_starts, dim3(g), dim3(kBlock), 0, s, head, run_of, n, run_start);
@@ -765,7 +763,7 @@ int h3d_ma_stats(h3d_ctx* ctx, const double* scaled, int64_t n, int R, int C,
     hipLaunchKernelGGL(k_flag_to_int, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_loop, n,
                        d_flag);
     if (int rc = cub_call(ctx, "cub_tmp_diag_s", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_flag, d_qpos, (int)n, s);
+          return exclusive_sum(tmp, bytes, d_flag, d_qpos, (int)n, s);
         }))
       return rc;
     // the loop pixels must be as many as the q-values, before q is indexed

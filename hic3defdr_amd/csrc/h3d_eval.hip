@@ -15,7 +15,6 @@
 // launch grid. No floating-point atomics: counts come from integer scans,
 // ballots and integer atomics. n < 2^31 throughout.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -23,6 +22,7 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_cub.h"
 #include "h3d_devutil.h"
 #include "h3d_errors.h"
 
@@ -110,7 +110,7 @@ int launch_membership(h3d_ctx* ctx, const int64_t* d_row, const int64_t* d_col, 
   hipLaunchKernelGGL(k_mem_set_keys, dim3(grid_for(ctx, k)), dim3(kBlock), 0, s, d_prow, d_pcol,
                      k, keys);
   if (int rc = cub_call(ctx, "cub_tmp_eval", [&](void* tmp, size_t& bytes) {
-        return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys, keys_s, (int)k, 0, 64, s);
+        return sort_keys(tmp, bytes, keys, keys_s, (int)k, 0, 64, s);
       }))
     return rc;
   hipLaunchKernelGGL(k_mem_query, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_row, d_col, n,
@@ -290,14 +290,13 @@ int launch_roc(h3d_ctx* ctx, const uint8_t* d_labels, const double* d_scores, in
   if (!sc.ok) return fail(H3D_ENOMEM, "roc buffers");
   int64_t* packed = (int64_t*)keys;  // SortPairs leaves its input unread afterwards
   auto sort = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, keys_s, d_labels, lab_s, (int)n,
-                                              0, 64, s);
+    return sort_pairs(tmp, bytes, keys, keys_s, d_labels, lab_s, (int)n, 0, 64, s);
   };
   auto scan_marks = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceScan::InclusiveSum(tmp, bytes, packed, cum, (int)n, s);
+    return inclusive_sum(tmp, bytes, packed, cum, (int)n, s);
   };
   auto scan_keep = [&](void* tmp, size_t& bytes) {
-    return hipcub::DeviceScan::InclusiveSum(tmp, bytes, keep, pos, (int)n, s);
+    return inclusive_sum(tmp, bytes, keep, pos, (int)n, s);
   };
   // one temp for the three, reserved at the largest before the first runs
   size_t tb = 0, tb2 = 0, tb3 = 0;
@@ -561,7 +560,7 @@ int h3d_order_stats(h3d_ctx* ctx, const double* values, int64_t n, const int64_t
     hipLaunchKernelGGL(k_os_keys, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_v, n, keys,
                        d_nan);
     if (int rc = cub_call(ctx, "cub_tmp_eval", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys, keys_s, (int)n, 0, 64, s);
+          return sort_keys(tmp, bytes, keys, keys_s, (int)n, 0, 64, s);
         }))
       return rc;
     if (K > 0) hipLaunchKernelGGL(k_os_pick, dim3(1), dim3(64), 0, s, keys_s, rk, K, d_res);

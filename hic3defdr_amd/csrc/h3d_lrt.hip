@@ -9,7 +9,6 @@
 #include "h3d.h"
 #include "h3d_ctx.h"
 #include "h3d_errors.h"
-#include "h3d_kernels.h"
 #include "h3d_lrt_group.h"
 
 using namespace h3d;
@@ -28,21 +27,21 @@ void launch_lrt(h3d_ctx* ctx, const int32_t* raw, const double* f,
                 int* flags, int wide) {
   if constexpr (M <= 8) {
     if (refit && dist && !wide)  // the pipeline's call (k_lrt TAB)
-      hipLaunchKernelGGL((k_lrt<M, CM, true>), dim3(grid_for(ctx, n, 16)), dim3(kBlock),
+      hipLaunchKernelGGL((k_lrt<M, CM, true>), dim3(grid_for(ctx, n, 16)), dim3(kLrtBlock),
                          0, ctx->stream, raw, f, dist, table, n, R, C, D, cond, refit,
                          p, llr, mu0, mu1, disp, flags, wide);
     else
-      hipLaunchKernelGGL((k_lrt<M, CM>), dim3(grid_for(ctx, n, 16)), dim3(kBlock), 0,
+      hipLaunchKernelGGL((k_lrt<M, CM>), dim3(grid_for(ctx, n, 16)), dim3(kLrtBlock), 0,
                          ctx->stream, raw, f, dist, table, n, R, C, D, cond, refit, p,
                          llr, mu0, mu1, disp, flags, wide);
   } else {
     if (refit && dist && !wide)  // the pipeline's call (k_lrt8 TAB)
       hipLaunchKernelGGL((k_lrt8<M, CM, true>), dim3(grid_for(ctx, n * kGroup, 16)),
-                         dim3(kBlock), 0, ctx->stream, raw, f, dist, table, n, R, C,
+                         dim3(kLrtBlock), 0, ctx->stream, raw, f, dist, table, n, R, C,
                          D, cond, refit, p, llr, mu0, mu1, disp, flags, wide);
     else
       hipLaunchKernelGGL((k_lrt8<M, CM>), dim3(grid_for(ctx, n * kGroup, 16)),
-                         dim3(kBlock), 0, ctx->stream, raw, f, dist, table, n, R, C,
+                         dim3(kLrtBlock), 0, ctx->stream, raw, f, dist, table, n, R, C,
                          D, cond, refit, p, llr, mu0, mu1, disp, flags, wide);
   }
 }

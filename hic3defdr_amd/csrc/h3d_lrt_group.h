@@ -14,7 +14,7 @@
 // its loops together.
 #pragma once
 
-#include "h3d_kernels.h"
+#include "h3d_lrt_kernel.h"
 
 namespace h3d {
 
@@ -124,7 +124,7 @@ template <int M, int CM, bool TAB = false>
 // rows the M = 32 instantiation grew into AGPRs at 1 wave -- cfg4 lrt 22.7
 // -> 31.0 ms, r03i --, while the rows still carried the cancelling prefix;
 // without it the rows take the table log from LDS, as k_lrt.)
-__global__ __launch_bounds__(kBlock, 2) void k_lrt8(
+__global__ __launch_bounds__(kLrtBlock, 2) void k_lrt8(
     const int32_t* __restrict__ raw, const double* __restrict__ f,
     const int32_t* __restrict__ dist, const double* __restrict__ table,
     int64_t n, int R, int C, int D, const int32_t* __restrict__ cond_of_rep,

@@ -15,13 +15,15 @@
 #include "h3d.h"
 #include "h3d_ctx.h"
 #include "h3d_errors.h"
-#include "h3d_kernels.h"
+#include "h3d_model.h"
 
 using namespace h3d;
 using namespace h3dint;
 using h3derr::fail;
 
 namespace {
+
+constexpr int kBlock = kLaunchBlock;
 
 // A lane's row of R values into M register slots (every index a compile-time
 // constant). `vec` = values per load: the host passes 4 / 2 only when R is a

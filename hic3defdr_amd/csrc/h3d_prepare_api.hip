@@ -2,7 +2,6 @@
 // matrices, size factors of every norm); shares the ctx / scratch / error
 // helpers of h3d_api.hip through h3d_ctx.h.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -10,9 +9,9 @@
 
 #include "h3d.h"
 #include "h3d_ctx.h"
+#include "h3d_cub.h"
 #include "h3d_errors.h"
 #include "h3d_host.h"
-#include "h3d_kernels.h"
 #include "h3d_prepare.h"
 
 using namespace h3d;
@@ -20,6 +19,8 @@ using namespace h3dint;
 using h3derr::fail;
 
 namespace {
+
+constexpr int kBlock = kLaunchBlock;
 
 // h3d_union_count reads as its stages; what they share travels in a
 // UnionCall, their results in ctx->prep (for h3d_union_fill).
@@ -100,7 +101,7 @@ int union_stage_replicate(UnionCall& u, int r) {
   hipLaunchKernelGGL(k_union_flags, dim3(grid_for(ctx, m)), dim3(kBlock), 0, s, u.d_row,
                      u.d_col, u.d_val, m, u.n_bins, u.dist_max, u.d_flag);
   if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& tb) {
-        return hipcub::DeviceScan::ExclusiveSum(tmp, tb, u.d_flag, u.d_pos, (int)m, s);
+        return exclusive_sum(tmp, tb, u.d_flag, u.d_pos, (int)m, s);
       }))
     return rc;
   int32_t last[2] = {0, 0};
@@ -139,14 +140,14 @@ int union_sort_runs(UnionCall& u) {
   P.run_of = sc.get<int32_t>("u_run_incl", tot);
   if (!sc.ok) return fail(H3D_ENOMEM, "union scratch");
   if (int rc = cub_call(ctx, "cub_tmp_u", [&](void* tmp, size_t& tb) {
-        return hipcub::DeviceRadixSort::SortPairs(tmp, tb, u.d_keys, P.keys_sorted, u.d_ent,
-                                                  P.ent_sorted, (int)tot, 0, u.end_bit, s);
+        return sort_pairs(tmp, tb, u.d_keys, P.keys_sorted, u.d_ent, P.ent_sorted, (int)tot, 0,
+                          u.end_bit, s);
       }))
     return rc;
   hipLaunchKernelGGL(k_run_heads, dim3(grid_for(ctx, tot)), dim3(kBlock), 0, s, P.keys_sorted,
                      tot, u.sentinel, u.d_head);
   if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& tb) {
-        return hipcub::DeviceScan::InclusiveSum(tmp, tb, u.d_head, P.run_of, (int)tot, s);
+        return inclusive_sum(tmp, tb, u.d_head, P.run_of, (int)tot, s);
       }))
     return rc;
   int32_t n_runs = 0;
@@ -174,7 +175,7 @@ int union_keep_runs(UnionCall& u) {
                      P.keys_sorted, P.ent_sorted, P.run_start, n_runs, tot, u.sentinel,
                      P.ent_rep, P.ent_val, u.R, u.n_bins, P.bias, keep);
   if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& tb) {
-        return hipcub::DeviceScan::InclusiveSum(tmp, tb, keep, P.px_of_run, (int)n_runs, s);
+        return inclusive_sum(tmp, tb, keep, P.px_of_run, (int)n_runs, s);
       }))
     return rc;
   int32_t n_px = 0;
@@ -281,9 +282,8 @@ int h3d_disp_pixels_dev(h3d_ctx* ctx, const int32_t* d_row, const int32_t* d_col
   double* d_bias = sc.get<double>("dp_bias", (size_t)n_bins * R);
   if (!sc.ok) return fail(H3D_ENOMEM, "disp pixel scratch");
   if (int rc = h2d_pinned(ctx, d_bias, bias, (size_t)n_bins * R * 8, s)) return rc;
-  hipcub::CountingInputIterator<int32_t> it(0);
   if (int rc = cub_call(ctx, "cub_tmp_sel", [&](void* tmp, size_t& bytes) {
-        return hipcub::DeviceSelect::Flagged(tmp, bytes, it, d_disp_idx, d_sel, d_cnt, (int)n, s);
+        return select_flagged_indices(tmp, bytes, d_disp_idx, d_sel, d_cnt, (int)n, s);
       }))
     return rc;
   int32_t cnt = 0;
@@ -474,7 +474,7 @@ int sf_order_and_bins(SfCall& c) {
   c.d_sf = sc.get<double>("sf_out", n * R);
   if (int rc = c.hc->ready("size factor scratch")) return rc;
   c.bal = c.d_balanced ? c.d_balanced : d_bal;
-  hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_idx, n);
+  launch_iota(ctx, s, c.d_idx, n);
   if (!c.conditional) {
     HIP_TRY(hipMemcpyAsync(c.d_perm, c.d_idx, n * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(c.d_bin, 0, n * 4, s));
@@ -482,8 +482,7 @@ int sf_order_and_bins(SfCall& c) {
     if (int rc = h2d_pinned(ctx, c.d_dist, c.dist, n * 4, s)) return rc;
     // stable sort by distance (the pinned equal_bin tie order)
     if (int rc = cub_call(ctx, "cub_tmp_sf", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, c.d_dist, c.d_dist_s, c.d_idx,
-                                                    c.d_perm, (int)n, 0, 31, s);
+          return sort_pairs(tmp, bytes, c.d_dist, c.d_dist_s, c.d_idx, c.d_perm, (int)n, 0, 31, s);
         }))
       return rc;
     if (c.n_bins > 0) {
@@ -496,7 +495,7 @@ int sf_order_and_bins(SfCall& c) {
       hipLaunchKernelGGL(k_dist_heads, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_dist_s,
                          n, d_head);
       if (int rc = cub_call(ctx, "cub_tmp_s", [&](void* tmp, size_t& bytes) {
-            return hipcub::DeviceScan::InclusiveSum(tmp, bytes, d_head, c.d_bin, (int)n, s);
+            return inclusive_sum(tmp, bytes, d_head, c.d_bin, (int)n, s);
           }))
         return rc;
       hipLaunchKernelGGL(k_minus_one, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_bin, n);
@@ -545,9 +544,8 @@ int sf_bin_factors_mor(SfCall& c) {
   if (int rc = h2d_pinned(ctx, d_segb, segb.data(), segb.size() * 8, s)) return rc;
   if (int rc = h2d_pinned(ctx, d_sege, sege.data(), sege.size() * 8, s)) return rc;
   if (int rc = cub_call(ctx, "cub_tmp_seg", [&](void* tmp, size_t& bytes) {
-        return hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, bytes, d_keys, d_keys_s,
-                                                          (int)(n * R), nb * R, d_segb, d_sege,
-                                                          0, 64, s);
+        return segmented_sort_keys(tmp, bytes, d_keys, d_keys_s, (int)(n * R), nb * R, d_segb,
+                                   d_sege, 0, 64, s);
       }))
     return rc;
   hipLaunchKernelGGL(k_mor_median, dim3((nb * R + 255) / 256), dim3(256), 0, s, d_keys_s,
@@ -574,12 +572,12 @@ int sf_bin_factors_scaling(SfCall& c) {
     if (!sc.ok) return fail(H3D_ENOMEM, "member scratch");
     hipLaunchKernelGGL(k_scatter_bin, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, c.d_perm,
                        c.d_bin, n, d_bin_orig);
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(ctx, n)), dim3(kBlock), 0, s, d_iota, n);
+    launch_iota(ctx, s, d_iota, n);
     int end_bit = 1;
     while (end_bit < 31 && (1 << end_bit) <= nb) ++end_bit;
     if (int rc = cub_call(ctx, "cub_tmp_sf", [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, d_bin_orig, d_bin_orig_s, d_iota,
-                                                    members, (int)n, 0, end_bit, s);
+          return sort_pairs(tmp, bytes, d_bin_orig, d_bin_orig_s, d_iota, members, (int)n, 0,
+                            end_bit, s);
         }))
       return rc;
   }
