@@ -339,8 +339,15 @@ struct DispCall {
   bool dual = false;
   HostStamps stamp;
   // the pixels sorted by distance, replicate-major rows; pseudodata
-  int32_t *raw_s = nullptr, *dist_s = nullptr;
+  int32_t* raw_s = nullptr;
   double *f_s = nullptr, *pd = nullptr;
+  // H3D_EQ_GATHER on the packed path of the single-rank driver: the prep
+  // only sorts, and the first equalize launch gathers the rows itself, from
+  // every condition's sort order (perm + c n) and packed records (packed +
+  // c n); gather_rows is cleared once that launch is enqueued
+  bool gather_rows = false;
+  const int32_t* perm = nullptr;
+  const CondPack2* packed = nullptr;
   int64_t* d_seg = nullptr;         // D + 1 segment bounds
   std::vector<int64_t> seg_start;   // their host copy (host-built tables)
   // chunk and segment tables, work list, per-segment state and results
@@ -391,19 +398,29 @@ struct DispCall {
 // (NLL: the multi-rank driver) the NLL-only pass (light)
 // (kFull: every condition has exactly M replicates -- k_disp_work's
 // replicate count is the constant M, see k_brent)
+// (c.gather_rows: the call's first equalize launch, which gathers the rows it
+// works on -- k_disp_work's kGather -- and leaves them for the later ones)
 template <int M, bool NLL, bool kFull = false>
-void launch_disp_work(const DispCall& c) {
+void launch_disp_work(DispCall& c) {
   h3d_ctx* ctx = c.ctx;
   auto launch = [&](auto k) {
     hipLaunchKernelGGL(k, dim3(work_grid(ctx, k, c.max_items)), dim3(kBlock), 0, c.s, c.raw_s,
                        c.f_s, c.pd, c.n, c.d_cs, c.d_cl, c.d_cd, c.C, c.d_repidx, c.d_nrep,
-                       c.d_st, c.d_flags, c.d_list, c.d_meta, c.d_partial, ctx->eq_static8);
+                       c.d_st, c.d_flags, c.d_list, c.d_meta, c.d_partial, ctx->eq_static8,
+                       c.perm, c.packed);
   };
   {
     ProfScope ps(ctx, "disp_work", 0, 1);
     // the equalize register budget: 4 waves per SIMD up to M = 8 (the sweeps
     // are in DESIGN.md, "Settled switches")
-    launch(k_disp_work<M, (M <= 8 ? 4 : 1), kEqualize, NLL, kFull>);
+    bool gathered = false;
+    if constexpr (M == 2 && !NLL)
+      if (c.gather_rows) {
+        launch(k_disp_work<M, 4, kEqualize, NLL, kFull, true>);
+        c.gather_rows = false;
+        gathered = true;
+      }
+    if (!gathered) launch(k_disp_work<M, (M <= 8 ? 4 : 1), kEqualize, NLL, kFull>);
   }
   if constexpr (NLL) {
     ProfScope ps(ctx, "disp_nll", 0);
@@ -494,7 +511,10 @@ int validate_and_plan(DispCall& c, const int32_t* cond_of_rep, int estimator) {
 // the LDS bitonic sorts LDS-bound (555 us); the radix passes stage their
 // scatter through LDS.) A distance outside the key's range, a negative one
 // included, saturates to the largest code, which is >= D: such pixels sort
-// behind every segment and the segment check rejects the call.
+// behind every segment and the segment check rejects the call. The segment
+// bounds are searched in condition 0's sorted keys (k_seg_bounds). idx_out:
+// n entries, or (c.gather_rows) C x n, a sort order per condition that the
+// first equalize launch gathers through instead of a gather kernel here.
 template <typename K>
 int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* idx_out) {
   h3d_ctx* ctx = c.ctx;
@@ -514,6 +534,11 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
   const bool pack = k32 && c.mslot == 2;
   int32_t* d_nrep = nullptr;
   CondPack2* packed = nullptr;
+  // c.gather_rows (sort_and_gather, implies pack): the prep only sorts, each
+  // condition into a sort order of its own (idx_out + c n), which with the
+  // records stays as it is until the first equalize launch has gathered
+  // through it (k_disp_work's kGather)
+  const bool fused = c.gather_rows;
   if (pack) {
     d_nrep = sc.get<int32_t>("sort_nrep", (size_t)C);
     packed = sc.get<CondPack2>("cond_pack2", (size_t)C * n);
@@ -540,7 +565,7 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
   // fork: no slot is regrown while a stream works on it. Without the extra
   // buffers (or the stream) the prep stays on one stream, and so does a call
   // of more than kPrepForkMaxPx pixels: the overlap wins a fixed amount per
-  // call (the sorts' short fill and histogram kernels, k_key_dist, launch
+  // call (the sorts' short fill and histogram kernels, k_seg_bounds, launch
   // gaps) and loses in proportion to n, since sort passes and gathers that
   // each fill the chip slow each other down. Parent
   // against two streams, prep per step: cfg2 (3.8 M pixels) 0.60 -> 0.51 ms,
@@ -551,7 +576,7 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
     Scratch sb{ctx};
     size_t tmp_bytes = 0;
     side.keys_s = sb.template get<K>("dkeys_s_b", n);
-    side.idx_out = sb.template get<int32_t>("idx_out_b", n);
+    if (!fused) side.idx_out = sb.template get<int32_t>("idx_out_b", n);
     if (!pack) side.keys = sb.template get<K>("dkeys_b", n);
     side.tmp_slot = "cub_tmp_b";
     two = sb.ok && radix_sort_temp_bytes<K>(n, 0, sort_bits, &tmp_bytes) == 0 &&
@@ -576,27 +601,33 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
   };
   auto sort_gather = [&](int cc, const Branch& b) -> int {
     const K* keys_c = pack ? keys + (size_t)cc * n : b.keys;
-    if (int rc = radix_sort_pairs<K>(ctx, b.tmp_slot, b.s, keys_c, b.keys_s, idx_in, b.idx_out,
-                                     n, 0, sort_bits))
+    int32_t* perm_c = fused ? idx_out + (size_t)cc * n : b.idx_out;
+    if (int rc = radix_sort_pairs<K>(ctx, b.tmp_slot, b.s, keys_c, b.keys_s, idx_in, perm_c, n, 0,
+                                     sort_bits))
       return rc;
-    if (cc == 0)
-      hipLaunchKernelGGL(k_key_dist<K>, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s,
-                         (const K*)b.keys_s, n, cbits, c.dist_s);
     SoaRows rows;
     for (int j = 0; j < c.nrep[cc]; ++j) {
       const int r = c.rep_idx[(size_t)cc * kMaxReps + j];
       rows.raw[j] = c.raw_s + (size_t)r * n;
       rows.f[j] = c.f_s + (size_t)r * n;
     }
-    if (pack) {
-      hipLaunchKernelGGL(k_gather_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s,
-                         b.idx_out, packed + (size_t)cc * n, n, c.nrep[cc], rows);
-      return 0;
+    if (fused) {
+      // (no gather here: the first equalize launch fills the rows)
+    } else if (pack) {
+      hipLaunchKernelGGL(k_gather_pack2, dim3(grid_for(ctx, n)), dim3(kBlock), 0, b.s, perm_c,
+                         packed + (size_t)cc * n, n, c.nrep[cc], rows);
+    } else {
+      const int64_t tiles = (n + kGatherTile - 1) / kGatherTile;
+      const int grid =
+          (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)ctx->n_cu * 8));
+      hipLaunchKernelGGL(k_gather_cond_tile, dim3(grid), dim3(256), 0, b.s, perm_c, c.d_raw,
+                         c.d_f, n, R, d_reps + cc * kMaxReps, c.nrep[cc], rows);
     }
-    const int64_t tiles = (n + kGatherTile - 1) / kGatherTile;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)ctx->n_cu * 8));
-    hipLaunchKernelGGL(k_gather_cond_tile, dim3(grid), dim3(256), 0, b.s, b.idx_out, c.d_raw,
-                       c.d_f, n, R, d_reps + cc * kMaxReps, c.nrep[cc], rows);
+    // the segment bounds out of condition 0's sorted keys, the distance above
+    // their cbits count bits, before the branch's next sort rewrites them
+    if (cc == 0)
+      hipLaunchKernelGGL(k_seg_bounds<K>, dim3((c.D + 1 + 255) / 256), dim3(256), 0, b.s,
+                         (const K*)b.keys_s, n, cbits, c.D, c.d_seg);
     return 0;
   };
   key_pass(0, main);
@@ -612,11 +643,16 @@ int sort_by_condition(DispCall& c, int end_bit, const int32_t* idx_in, int32_t* 
     key_pass(cc, side);
     if (int rc = sort_gather(cc, side)) return rc;
   }
+  if (fused) {
+    c.perm = idx_out;
+    c.packed = packed;
+  }
   return 0;
 }
 
-// Stage (n > 0): the pixels sorted by distance into SoA rows, the segment
-// bounds, and -- host-built tables -- the bounds on the host, checked.
+// Stage (n > 0): the pixels sorted by distance into SoA rows (gather_rows:
+// their sort orders, the rows left to the first equalize launch), the
+// segment bounds, and -- host-built tables -- the bounds on the host, checked.
 int sort_and_gather(DispCall& c) {
   h3d_ctx* ctx = c.ctx;
   const int64_t n = c.n;
@@ -632,22 +668,24 @@ int sort_and_gather(DispCall& c) {
     }
   } scope_end{c};
   Scratch sc{ctx};
+  int end_bit = 1;
+  while ((1 << end_bit) <= D) ++end_bit;
+  // H3D_EQ_GATHER: on the packed path (32-bit keys, <= 2 replicates per
+  // condition) of the single-rank driver the prep only sorts, into one sort
+  // order per condition, and the first equalize launch gathers
+  c.gather_rows = ctx->eq_gather && !c.reduce && end_bit <= 16 && c.mslot == 2;
   int32_t* idx_in = sc.get<int32_t>("idx_in", n);
-  int32_t* idx_out = sc.get<int32_t>("idx_out_c", n);
-  c.dist_s = sc.get<int32_t>("dist_s", n);
+  int32_t* idx_out = c.gather_rows ? sc.get<int32_t>("cond_perm", (size_t)c.C * n)
+                                   : sc.get<int32_t>("idx_out_c", n);
   c.raw_s = sc.get<int32_t>("raw_s", n * R);
   c.f_s = sc.get<double>("f_s", n * R);
   c.pd = sc.get<double>("pd", n * R);
   c.d_seg = sc.get<int64_t>("seg_start", D + 1);
   if (!sc.ok) return fail(H3D_ENOMEM, "device allocation failed (n=%lld)", (long long)n);
   launch_iota(ctx, c.s, idx_in, n);
-  int end_bit = 1;
-  while ((1 << end_bit) <= D) ++end_bit;
   if (int rc = end_bit <= 16 ? sort_by_condition<uint32_t>(c, end_bit, idx_in, idx_out)
                              : sort_by_condition<uint64_t>(c, end_bit, idx_in, idx_out))
     return rc;
-  hipLaunchKernelGGL(k_seg_bounds, dim3((D + 1 + 255) / 256), dim3(256), 0, c.s, c.dist_s, n,
-                     D, c.d_seg);
   c.stamp("prep launched");
   if (c.dev_tables) return 0;  // k_disp_tables checks the bounds
   HIP_TRY(hipMemcpyAsync(c.seg_start.data(), c.d_seg, (D + 1) * 8, hipMemcpyDeviceToHost, c.s));
@@ -825,7 +863,8 @@ int start_qcml(DispCall& c) {
   launch_seg_update(c, 1, 0);
   // the join of a forked prep: k_disp_tables, the table upload, the gang
   // setup and the list above need only the segment bounds; the equalize pass
-  // that comes next reads every condition's rows
+  // that comes next reads every condition's rows (gather_rows: its sort
+  // order)
   c.join_prep();
   if (!ctx->h_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_meta, 32, hipHostMallocDefault));
   c.h_meta = ctx->h_meta;
@@ -1122,6 +1161,7 @@ h3d_ctx* h3d_open(int device) {
   if (const char* e = std::getenv("H3D_NLL_FULL")) ctx->nll_full = std::atoi(e);
   if (const char* e = std::getenv("H3D_NLL_RANGES")) ctx->nll_ranges = std::atoi(e);
   if (const char* e = std::getenv("H3D_PREP_STREAMS")) ctx->prep_streams = std::atoi(e);
+  if (const char* e = std::getenv("H3D_EQ_GATHER")) ctx->eq_gather = std::atoi(e);
   if (const char* e = std::getenv("H3D_GANG_P")) ctx->gang_px = std::atoi(e);
   if (hipMalloc((void**)&ctx->work_count, 2 * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(ctx->work_count, 0, 2 * sizeof(unsigned long long)) != hipSuccess) {

@@ -160,6 +160,11 @@ struct h3d_ctx {
   // call too large to gain from it stays on `stream`, sort_by_condition);
   // 1 = everything on `stream`, one condition after the other
   int prep_streams = 2;
+  // H3D_EQ_GATHER: 1 = on the packed path of the single-rank driver (32-bit
+  // keys, every condition <= 2 replicates) the prep only sorts and the first
+  // equalize launch gathers the sorted rows itself (k_disp_work's kGather;
+  // the same bits); 0 = a gather kernel per condition in the prep
+  int eq_gather = 1;
   // created by h3d_open with the switch at 2 (early: a stream created when
   // the process's hardware queues are all taken shares one, and two streams
   // on one queue run in enqueue order), destroyed with the ctx

@@ -218,23 +218,18 @@ static __global__ void k_gather_pack2(const int32_t* __restrict__ perm,
   }
 }
 
+// seg_start[d] = first index whose distance is >= d (d = 0..D), searched in
+// condition 0's sorted keys: the distance is the key above its cbits count
+// bits (a saturated one is >= D and lands behind every segment)
 template <typename K>
-__global__ void k_key_dist(const K* __restrict__ keys, int64_t n, int cbits,
-                           int32_t* __restrict__ dist_s) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    dist_s[i] = (int32_t)((uint64_t)keys[i] >> cbits);
-}
-
-// seg_start[d] = first index with dist_s >= d (d = 0..D)
-static __global__ void k_seg_bounds(const int32_t* __restrict__ dist_s, int64_t n,
-                             int D, int64_t* __restrict__ seg_start) {
+__global__ void k_seg_bounds(const K* __restrict__ keys_s, int64_t n, int cbits, int D,
+                             int64_t* __restrict__ seg_start) {
   const int d = blockIdx.x * blockDim.x + threadIdx.x;
   if (d > D) return;
   int64_t lo = 0, hi = n;
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
-    if (dist_s[mid] < d)
+    if ((int64_t)((uint64_t)keys_s[mid] >> cbits) < d)
       lo = mid + 1;
     else
       hi = mid;
@@ -358,16 +353,31 @@ constexpr int kWorkMetaInts = kTaskHeadStride * 17;
 // fit_mu's replicate tests. The same bits. 128 VGPRs and 16 B of scratch at 4
 // waves (the general instantiation 32 B); measured on cfg2, equalize 2.55-2.57
 // -> 2.43-2.45 ms per step (profiles/r07).
-template <int M, int W, int PH, bool NLL = true, bool kFull = false>
+// kGather (the first equalize launch of a single-rank call on the packed
+// path, M = 2, H3D_EQ_GATHER): the sorted rows do not exist yet. The lane of
+// pixel position px of condition c reads the record packed[c n + perm[c n +
+// px]] (k_gather_pack2's two 16-byte loads), takes its counts and factors as
+// x and f and stores them to the rows, which the later launches and nothing
+// before them read: that launch visits every pixel of every condition once,
+// so the gather's pass over memory runs under its arithmetic. The same values
+// into the same functions: the same bits.
+template <bool kWrite, typename T>
+using RowPtr = std::conditional_t<kWrite, T*, const T*>;
+
+template <int M, int W, int PH, bool NLL = true, bool kFull = false, bool kGather = false>
 __global__ __launch_bounds__(kBlock, W) void k_disp_work(
-    const int32_t* __restrict__ raw_s, const double* __restrict__ f_s,
+    RowPtr<kGather, int32_t> __restrict__ raw_s, RowPtr<kGather, double> __restrict__ f_s,
     double* __restrict__ pd, int64_t n, const int64_t* __restrict__ chunk_start,
     const int32_t* __restrict__ chunk_len, const int32_t* __restrict__ chunk_d,
     int C, const int32_t* __restrict__ rep_idx /* C x kMaxReps */,
     const int32_t* __restrict__ n_rep /* C */, const SegState* __restrict__ st,
     int* __restrict__ seg_flags, const int32_t* __restrict__ list,
     int32_t* __restrict__ meta /* [len, active, eq_len, live], task heads */,
-    double* __restrict__ partial, int static8) {
+    double* __restrict__ partial, int static8,
+    const int32_t* __restrict__ perm /* kGather: C x n */,
+    const CondPack2* __restrict__ packed /* kGather: C x n */) {
+  static_assert(!kGather || (M == 2 && PH == kEqualize && !NLL),
+                "the gathering launch is the single-rank equalize pass at M = 2");
   const int beg = (PH == kEqualize) ? 0 : meta[2];
   const int end = (PH == kEqualize) ? meta[2] : meta[0];
   // Tasks are (item, wave) pairs: wave q of a block evaluates pixels
@@ -442,13 +452,34 @@ __global__ __launch_bounds__(kBlock, W) void k_disp_work(
       if (phase == kEqualize) {
         const double alpha = st[s].disp;
         double x[MS], f[MS], as[MS], lf[MS];
+        if constexpr (kGather) {
+          const int64_t cn = (int64_t)c * n;
+          const int4* rec = reinterpret_cast<const int4*>(packed + cn + perm[cn + px]);
+          const int4 rv = rec[0];
+          const double2 fv = reinterpret_cast<const double2*>(rec + 1)[0];
+          const int rw[2] = {rv.x, rv.y};
+          const double fw[2] = {fv.x, fv.y};
 #pragma unroll
-        for (int k = 0; k < MS; ++k) {
-          const bool on = k < nr;
-          x[k] = on ? (double)raw_s[(int64_t)ri[k] * n + px] : 0.0;
-          f[k] = on ? f_s[(int64_t)ri[k] * n + px] : 1.0;
-          lf[k] = on ? log_fast_checked(f[k], s_tab) : 0.0;
-          as[k] = alpha;
+          for (int k = 0; k < MS; ++k) {
+            const bool on = k < nr;  // (one replicate: row 0 only, as the gather)
+            if (on) {
+              raw_s[(int64_t)ri[k] * n + px] = rw[k];
+              f_s[(int64_t)ri[k] * n + px] = fw[k];
+            }
+            x[k] = on ? (double)rw[k] : 0.0;
+            f[k] = on ? fw[k] : 1.0;
+            lf[k] = on ? log_fast_checked(f[k], s_tab) : 0.0;
+            as[k] = alpha;
+          }
+        } else {
+#pragma unroll
+          for (int k = 0; k < MS; ++k) {
+            const bool on = k < nr;
+            x[k] = on ? (double)raw_s[(int64_t)ri[k] * n + px] : 0.0;
+            f[k] = on ? f_s[(int64_t)ri[k] * n + px] : 1.0;
+            lf[k] = on ? log_fast_checked(f[k], s_tab) : 0.0;
+            as[k] = alpha;
+          }
         }
         int fl = 0;
         H3D_SEC_BEGIN(t_fit);
@@ -489,6 +520,9 @@ __global__ __launch_bounds__(kBlock, W) void k_disp_work(
             lo &= lo - 1u;
           }
           const int64_t o = (int64_t)ri[k] * n + px;
+          // (kGather: this lane has just stored both. Keeping them in
+          // registers across q2q instead cost the general instantiation 16 B
+          // more scratch than its parent has)
           double mu_in = mu * f_s[o];
           double mu_out = (k > fc) ? 0.25 : mu_out0;
           H3D_SEC_BEGIN(t_q2q);

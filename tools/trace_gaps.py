@@ -3,7 +3,8 @@ step (a step starts at the k_iota launch of estimate_disp's sort): kernel
 busy time, span, and the gaps longer than a threshold with the kernels on
 either side -- where the host holds the GPU up. With ``prep`` also the last
 step's prep, k_iota to the first equalize launch (k_disp_work), kernel by
-kernel with its hardware queue: start and end in us from the first key
+kernel with its hardware queue (and that first equalize launch as the last
+row): start and end in us from the first key
 kernel, the span of the prep and the time two of its kernels ran at once
 (the two-stream prep, H3D_PREP_STREAMS=2).
 
@@ -53,7 +54,7 @@ def prep(st, queue):
     t0 = next((r[0] for r in ks if 'k_dist_cond_keys' in r[2]), ks[0][0])
     print('prep of the last step, us from the first key kernel:')
     print('   %8s %8s %7s  %-5s %s' % ('start', 'end', 'us', 'queue', 'kernel'))
-    for r in ks:
+    for r in ks + [st[end]]:  # (the last row: the first equalize launch)
         print('   %8.1f %8.1f %7.1f  %-5s %s' % (
             (r[0] - t0) / 1e3, (r[1] - t0) / 1e3, (r[1] - r[0]) / 1e3,
             queue[r], r[2]))
