@@ -46,6 +46,7 @@ EXPORTS = [
     'h3d_balance_pixels',
     'h3d_pixel_membership', 'h3d_pixel_membership_dev', 'h3d_roc_curve',
     'h3d_roc_curve_dev', 'h3d_order_stats', 'h3d_bin_fractions',
+    'h3d_nb_sample', 'h3d_nb_sample_dev', 'h3d_simulate_dev',
 ]
 
 
@@ -75,6 +76,8 @@ _INT_MAX = 2 ** 31 - 1
 _I64 = ctypes.c_int64
 _I = ctypes.c_int
 _D = ctypes.c_double
+_U64 = ctypes.c_uint64
+_U32 = ctypes.c_uint32
 ALLREDUCE_FN = ctypes.CFUNCTYPE(_I, ctypes.POINTER(_D), _I64, _P)
 
 _lib = None
@@ -194,6 +197,13 @@ def load_library(path=None):
                                          _P]),
             'h3d_nb_quantile_map': (_I, [_P, _P, _P, _P, _D, _P, _I64, _P]),
             'h3d_nb_logpmf': (_I, [_P, _P, _P, _P, _I64, _P]),
+            'h3d_nb_sample': (_I, [_P, _P, _P, _I64, _U64, _U32, _U32, _I64,
+                                   _P, _P, _P]),
+            'h3d_nb_sample_dev': (_I, [_P, _P, _P, _I64, _U64, _U32, _U32,
+                                       _I64, _P, _P, _P]),
+            'h3d_simulate_dev': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I,
+                                      _I64, _I, _I, _U64, _U32, _I64, _P,
+                                      _P]),
             'h3d_group_sums': (_I, [_P, _P, _P, _I64, _I, _I, _P, _P]),
             'h3d_group_sums_dev': (_I, [_P, _P, _P, _I64, _I, _I, _P, _P]),
             'h3d_histogram': (_I, [_P, _P, _I64, _P, _I, _P]),
@@ -249,6 +259,22 @@ def _wmode(weighted):
             raise ValueError('weighted must be a bool or "reference"')
         return 2
     return int(bool(weighted))
+
+
+def check_stream(seed, stream=0, rep=0, pixel0=0):
+    """The coordinates of the sampling stream (h3d_nb_sample) as Python ints:
+    ``seed`` an integer in [0, 2^63), ``stream`` and ``rep`` in [0, 2^32),
+    ``pixel0`` in [0, 2^62); ValueError otherwise (bool is not an integer
+    here)."""
+    out = []
+    for name, v, hi in (('seed', seed, 2 ** 63), ('stream', stream, 2 ** 32),
+                        ('rep', rep, 2 ** 32), ('pixel0', pixel0, 2 ** 62)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or \
+                not 0 <= int(v) < hi:
+            raise ValueError('%s must be an integer in [0, 2^%d), got %r'
+                             % (name, hi.bit_length() - 1, v))
+        out.append(int(v))
+    return tuple(out)
 
 
 def _ptr(a):
@@ -825,6 +851,97 @@ class Context(object):
                                       _ptr(phi), k.size, _ptr(out)),
                'h3d_nb_logpmf')
         return out
+
+    # -- negative-binomial sampling (util/simulation.py simulate_gpu) ---------
+    def nb_sample(self, bm, disp, seed, stream=0, rep=0, pixel0=0,
+                  want_lambda=False):
+        """One replicate's negative-binomial draws (h3d_nb_sample) for the
+        biased means ``bm`` (n) and dispersions ``disp`` (n): (counts (n)
+        int32, the gamma stage's lambda (n) or None, flags). Element i is
+        the draw of (seed, stream, rep, pixel0 + i). A bad element's count is
+        -1 and sets H3D_FLAG_BADIN (16) in flags."""
+        seed, stream, rep, pixel0 = check_stream(seed, stream, rep, pixel0)
+        bm = _c(bm, np.float64)
+        disp = _c(disp, np.float64)
+        if bm.ndim != 1 or disp.shape != bm.shape:
+            raise ValueError('bm and disp must both be (n,)')
+        counts = np.empty(bm.size, dtype=np.int32)
+        lam = np.empty(bm.size) if want_lambda else None
+        fl = _I(0)
+        _check(self.lib.h3d_nb_sample(
+            self.handle, _ptr(bm), _ptr(disp), bm.size, seed, stream, rep,
+            pixel0, _ptr(counts), _ptr(lam), ctypes.byref(fl)),
+            'h3d_nb_sample')
+        return counts, lam, fl.value
+
+    def nb_sample_dev(self, bm, disp, seed, stream=0, rep=0, pixel0=0,
+                      want_lambda=False):
+        """nb_sample on float64 torch tensors of this ctx's device; counts
+        and lambda come back as tensors."""
+        import torch
+        seed, stream, rep, pixel0 = check_stream(seed, stream, rep, pixel0)
+        if bm.dtype != torch.float64 or disp.dtype != torch.float64 or \
+                bm.dim() != 1 or disp.shape != bm.shape:
+            raise ValueError('bm and disp must both be float64 (n,)')
+        bm, disp = bm.contiguous(), disp.contiguous()
+        n = bm.numel()
+        counts = torch.empty(n, dtype=torch.int32, device=bm.device)
+        lam = torch.empty(n, dtype=torch.float64, device=bm.device) \
+            if want_lambda else None
+        fl = _I(0)
+        torch.cuda.current_stream(bm.device).synchronize()
+        _check(self.lib.h3d_nb_sample_dev(
+            self.handle, _P(bm.data_ptr()), _P(disp.data_ptr()), n, seed,
+            stream, rep, pixel0, _P(counts.data_ptr()),
+            _P(lam.data_ptr()) if want_lambda else None, ctypes.byref(fl)),
+            'h3d_nb_sample_dev')
+        return counts, lam, fl.value
+
+    def simulate_dev(self, row, col, mean_a, mean_b, bias, size_factors,
+                     table, seed, stream=0, pixel0=0):
+        """Every replicate of one chromosome (h3d_simulate_dev) on torch
+        tensors of this ctx's device: ``row`` / ``col`` (n) int32, ``mean_a``
+        / ``mean_b`` (n), ``bias`` (n_bins, J), ``size_factors`` (J,) or
+        (D, J), ``table`` (D,) float64 -> (counts (J, n) int32, flags).
+        Replicate j < J // 2 draws from mean_a, the others from mean_b."""
+        import torch
+        seed, stream, _, pixel0 = check_stream(seed, stream, 0, pixel0)
+        n = row.numel()
+        f64, i32 = torch.float64, torch.int32
+        if row.dtype != i32 or col.dtype != i32 or row.dim() != 1 or \
+                col.shape != row.shape:
+            raise ValueError('row and col must both be int32 (n,)')
+        if any(t.dtype != f64 for t in (mean_a, mean_b, bias, size_factors,
+                                        table)):
+            raise ValueError('means, bias, size factors and table must be '
+                             'float64')
+        if mean_a.shape != row.shape or mean_b.shape != row.shape:
+            raise ValueError('mean_a and mean_b must be (n,)')
+        if bias.dim() != 2 or not 1 <= bias.shape[1] <= 32:
+            raise ValueError('bias must be (n_bins, J), 1 <= J <= 32')
+        n_bins, J = bias.shape
+        if table.dim() != 1 or table.numel() < 1:
+            raise ValueError('table must be (D,), D >= 1')
+        D = table.numel()
+        if tuple(size_factors.shape) == (J,):
+            sf_rows = 1
+        elif tuple(size_factors.shape) == (D, J):
+            sf_rows = D
+        else:
+            raise ValueError('size_factors must be (J,) or (D, J)')
+        row, col, mean_a, mean_b, bias, size_factors, table = (
+            t.contiguous() for t in (row, col, mean_a, mean_b, bias,
+                                     size_factors, table))
+        counts = torch.empty((J, n), dtype=i32, device=row.device)
+        fl = _I(0)
+        torch.cuda.current_stream(row.device).synchronize()
+        _check(self.lib.h3d_simulate_dev(
+            self.handle, _P(row.data_ptr()), _P(col.data_ptr()),
+            _P(mean_a.data_ptr()), _P(mean_b.data_ptr()),
+            _P(bias.data_ptr()), _P(size_factors.data_ptr()), sf_rows,
+            _P(table.data_ptr()), D, n, J, n_bins, seed, stream, pixel0,
+            _P(counts.data_ptr()), ctypes.byref(fl)), 'h3d_simulate_dev')
+        return counts, fl.value
 
     # -- diagnostics (util/diagnostics.py) -----------------------------------
     def group_sums(self, keys, values, K):

@@ -4,7 +4,7 @@ simulate(): per chromosome, the mean of a condition's scaled data, perturbed
 at that condition's loop clusters into two synthetic conditions A and B,
 re-biased with the real replicates' bias vectors and size factors, NB-drawn
 with the fitted dispersion function (host, the reference's global numpy
-random stream). evaluate(): ROC / FDR of this analysis' q-values (the GPU
+random stream; gpu=True: on the GPU from a counter-based stream). evaluate(): ROC / FDR of this analysis' q-values (the GPU
 pipeline's) against the simulation's true cluster labels.
 """
 import os
@@ -18,24 +18,44 @@ from hic3defdr_amd.util.clusters import load_clusters
 from hic3defdr_amd.util.evaluation import (evaluate, make_y_true,
                                            make_y_true_gpu)
 from hic3defdr_amd.util.printing import eprint
-from hic3defdr_amd.util.simulation import simulate
+from hic3defdr_amd.util.simulation import simulate, simulate_gpu
 
 
 class SimulatingHiC3DeFDR(object):
 
     def simulate(self, cond, chrom=None, beta=0.5, p_diff=0.4,
                  skip_bias=False, loop_pattern=None, outdir='sim',
-                 n_threads=-1, verbose=True):
+                 n_threads=-1, verbose=True, gpu=False, seed=None):
         """Reference ``simulation.py:22-144``. Writes
         ``<outdir>/<A|B><k>_<chrom>_raw.npz``, ``labels_<chrom>.txt`` and
         ``design.csv``. Chromosomes run in order (the random stream is
-        consumed chromosome by chromosome, as the reference's serial path)."""
+        consumed chromosome by chromosome, as the reference's serial path).
+
+        ``gpu=True`` (with an integer ``seed`` in [0, 2^63)): the same files
+        from ``util.simulation.simulate_gpu`` -- the draws on the GPU from a
+        counter-based stream, stream id = the chromosome's index in
+        ``self.chroms``. The counts differ from the host path's (a
+        different, documented stream), numpy's global
+        stream is neither read nor advanced, and a chromosome simulated
+        alone gets the files the whole-genome call gives it."""
+        if gpu:
+            try:
+                seed = _native.check_stream(seed)[0]
+            except ValueError:
+                raise ValueError('simulate(gpu=True) needs an integer seed '
+                                 'in [0, 2^63), got %r' % (seed,))
+        elif seed is not None:
+            raise ValueError('seed is for gpu=True: the host path draws from '
+                             "numpy's global stream (np.random.seed)")
         if chrom is None:
             for c in self.chroms:
                 self.simulate(cond, chrom=c, beta=beta, p_diff=p_diff,
                               skip_bias=skip_bias, loop_pattern=loop_pattern,
-                              outdir=outdir, verbose=verbose)
+                              outdir=outdir, verbose=verbose, gpu=gpu,
+                              seed=seed)
             return
+        if gpu and chrom not in self.chroms:
+            raise ValueError('chrom %r is not one of self.chroms' % (chrom,))
         eprint('simulating data for chrom %s' % chrom)
         loop_pattern = loop_pattern or self.loop_patterns[cond]
         reps = np.asarray(self.design[cond], dtype=bool)
@@ -65,9 +85,17 @@ class SimulatingHiC3DeFDR(object):
         if skip_bias:
             bias = np.ones_like(bias)
             sf = np.ones_like(sf)
-        classes, reps_iter = simulate(
-            row, col, mean, disp_fn, np.tile(bias, 2), np.tile(sf, 2),
-            clusters, beta=beta, p_diff=p_diff, trend='dist', verbose=verbose)
+        if gpu:
+            classes, reps_iter = simulate_gpu(
+                row, col, mean, disp_fn, np.tile(bias, 2), np.tile(sf, 2),
+                clusters, beta=beta, p_diff=p_diff, trend='dist', seed=seed,
+                stream=list(self.chroms).index(chrom), verbose=verbose,
+                ctx=self._ctx())
+        else:
+            classes, reps_iter = simulate(
+                row, col, mean, disp_fn, np.tile(bias, 2), np.tile(sf, 2),
+                clusters, beta=beta, p_diff=p_diff, trend='dist',
+                verbose=verbose)
         np.savetxt('%s/labels_%s.txt' % (outdir, chrom), classes, fmt='%s')
         for rep, csr in zip(repnames, reps_iter):
             sparse.save_npz('%s/%s_%s_raw.npz' % (outdir, rep, chrom), csr)

@@ -50,7 +50,8 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_bh.hip', 'hipcc'), ('h3d_table.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
                ('h3d_nb.hip', 'hipcc'), ('h3d_diag.hip', 'hipcc'),
-               ('h3d_eval.hip', 'hipcc'), ('h3d_ctx.hip', 'hipcc'),
+               ('h3d_eval.hip', 'hipcc'), ('h3d_sim.hip', 'hipcc'),
+               ('h3d_ctx.hip', 'hipcc'),
                ('h3d_cub_sort_idx.hip', 'hipcc'), ('h3d_cub_sort_int.hip', 'hipcc'),
                ('h3d_cub_sort_f64.hip', 'hipcc'), ('h3d_cub_scan.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]
@@ -62,7 +63,10 @@ HIP_FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC',
 # per-TU flags. h3d_nb.hip: every device function inlined -- with calls, the
 # frame of the out-of-line find_inverse_gamma (one callee-saved VGPR) gave
 # each k_nb_equalize / k_nb_quantile_map 16 B of scratch
-TU_FLAGS = {'h3d_nb.hip': ['-mllvm', '-amdgpu-function-calls=false']}
+TU_FLAGS = {'h3d_nb.hip': ['-mllvm', '-amdgpu-function-calls=false'],
+            # h3d_sim.hip: the same frames (find_inverse_gamma, poisson_tail)
+            # gave k_nb_sample / k_nb_sample_one 16 B of scratch
+            'h3d_sim.hip': ['-mllvm', '-amdgpu-function-calls=false']}
 
 
 def _digest(cmd, deps):

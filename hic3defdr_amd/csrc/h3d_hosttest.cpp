@@ -1,6 +1,7 @@
 // Host build of the device numerics, for CPU unit tests ONLY.
 //
-// The same headers the gfx950 kernels include (h3d_special.h, h3d_model.h)
+// The same headers the gfx950 kernels include (h3d_special.h, h3d_model.h,
+// h3d_philox.h, h3d_sample.h)
 // compiled with g++ and exported over a flat C ABI so tests/ can check them
 // against scipy / the oracle without a GPU. The product never loads this
 // library (hic3defdr_amd loads libh3d.so and fails loudly without it).
@@ -8,6 +9,8 @@
 #include <vector>
 
 #include "h3d_model.h"
+#include "h3d_philox.h"
+#include "h3d_sample.h"
 #include "h3d_special.h"
 
 namespace {
@@ -46,6 +49,72 @@ H3DT_UNARY(recip_fast, recip_fast)
 H3DT_BINARY(div_fast, div_fast)
 // exp_fast's gfx950 straight line evaluated here (host build only)
 H3DT_UNARY(exp_fast_straight, exp_fast_straight)
+
+// Philox4x32-10 of n (counter, key) pairs: ctr (n, 4), key (n, 2) -> out
+// (n, 4) words, and the stream's two uniforms of each output (u (n, 2))
+void h3dt_philox(int64_t n, const uint32_t* ctr, const uint32_t* key, uint32_t* out,
+                 double* u) {
+  for (int64_t i = 0; i < n; ++i) {
+    const h3d::Philox4 c = {ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3]};
+    const h3d::Philox4 o = h3d::philox4x32_10(c, key[2 * i], key[2 * i + 1]);
+    out[4 * i] = o.w0, out[4 * i + 1] = o.w1, out[4 * i + 2] = o.w2, out[4 * i + 3] = o.w3;
+    u[2 * i] = h3d::philox_uniform(o.w0, o.w1);
+    u[2 * i + 1] = h3d::philox_uniform(o.w2, o.w3);
+  }
+}
+
+// the stream's uniform of the words (lo[i], hi[i])
+void h3dt_philox_uniform(int64_t n, const uint32_t* lo, const uint32_t* hi, double* u) {
+  for (int64_t i = 0; i < n; ++i) u[i] = h3d::philox_uniform(lo[i], hi[i]);
+}
+
+// nb_draw elementwise: the gamma stage's lambda, the count k (-1: bad input)
+// and, optionally, the Poisson path taken (h3d_sample.h kPois*); returns the
+// OR of the flags
+int h3dt_nb_draw(int64_t n, const double* bm, const double* disp, const double* u1,
+                 const double* u2, double* lambda, int32_t* k, int32_t* path) {
+  int fl = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    int pth;
+    k[i] = h3d::nb_draw(bm[i], disp[i], u1[i], u2[i], &lambda[i], &fl, &pth);
+    if (path) path[i] = pth;
+  }
+  return fl;
+}
+
+// the biased means and dispersions h3d_simulate_dev draws from (its
+// arguments): bm and disp as (J, n) planes; -1 for a row / col outside
+// [0, n_bins) or a col - row outside [0, D)
+int h3dt_sim_bm(int64_t n, int J, int n_bins, int D, const int32_t* row,
+                const int32_t* col, const double* meanA, const double* meanB,
+                const double* bias, const double* sf, int sf_rows, const double* table,
+                double* bm, double* disp) {
+  for (int64_t i = 0; i < n; ++i)
+    if (row[i] < 0 || row[i] >= n_bins || col[i] < row[i] || col[i] >= n_bins ||
+        col[i] - row[i] >= D)
+      return -1;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t dist = (int64_t)col[i] - row[i];
+    for (int j = 0; j < J; ++j) {
+      const double s = sf[(sf_rows == 1 ? 0 : dist * J) + j];
+      bm[j * n + i] = h3d::sim_bm(j < J / 2 ? meanA[i] : meanB[i],
+                                  bias[(int64_t)row[i] * J + j],
+                                  bias[(int64_t)col[i] * J + j], s);
+      disp[j * n + i] = table[dist];
+    }
+  }
+  return 0;
+}
+
+// poisson_quantile elementwise (lambda >= 0 finite, u in (0, 1)); k as a double
+void h3dt_poisson_quantile(int64_t n, const double* lambda, const double* u, double* k,
+                           int32_t* path) {
+  for (int64_t i = 0; i < n; ++i) {
+    int pth;
+    k[i] = h3d::poisson_quantile(lambda[i], u[i], &pth);
+    if (path) path[i] = pth;
+  }
+}
 
 // igam_pq as q2q_core / igam_inv call it: lga = lgam_q2q(a), tail -1 / 0 / 1
 void h3dt_igam_pq(int64_t n, const double* a, const double* x, int tail,

@@ -19,6 +19,8 @@
 #include <vector>
 
 #include "h3d_model.h"
+#include "h3d_philox.h"
+#include "h3d_sample.h"
 #include "h3d_special.h"
 
 namespace {
@@ -81,6 +83,76 @@ __global__ void k_log_index(int64_t n, const double* __restrict__ x,
     const double m = frexp(x[i], &e);
     bits[i] = h3d::log_fast_index(m);
     fp[i] = h3d::log_fast_index_fp(m);
+  }
+}
+
+__global__ void k_philox(int64_t n, const uint32_t* __restrict__ ctr,
+                         const uint32_t* __restrict__ key, uint32_t* __restrict__ out,
+                         double* __restrict__ u) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const h3d::Philox4 c = {ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3]};
+    const h3d::Philox4 o = h3d::philox4x32_10(c, key[2 * i], key[2 * i + 1]);
+    out[4 * i] = o.w0;
+    out[4 * i + 1] = o.w1;
+    out[4 * i + 2] = o.w2;
+    out[4 * i + 3] = o.w3;
+    u[2 * i] = h3d::philox_uniform(o.w0, o.w1);
+    u[2 * i + 1] = h3d::philox_uniform(o.w2, o.w3);
+  }
+}
+
+__global__ void k_philox_uniform(int64_t n, const uint32_t* __restrict__ lo,
+                                 const uint32_t* __restrict__ hi, double* __restrict__ u) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    u[i] = h3d::philox_uniform(lo[i], hi[i]);
+}
+
+__global__ void k_nb_draw(int64_t n, const double* __restrict__ bm,
+                          const double* __restrict__ disp, const double* __restrict__ u1,
+                          const double* __restrict__ u2, double* __restrict__ lambda,
+                          int32_t* __restrict__ k, int32_t* __restrict__ path,
+                          int* __restrict__ status) {
+  int fl = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    double lam;
+    int pth;
+    k[i] = h3d::nb_draw(bm[i], disp[i], u1[i], u2[i], &lam, &fl, &pth);
+    lambda[i] = lam;
+    path[i] = pth;
+  }
+  if (fl) atomicOr(status, fl);
+}
+
+__global__ void k_sim_bm(int64_t n, int J, const int32_t* __restrict__ row,
+                         const int32_t* __restrict__ col, const double* __restrict__ meanA,
+                         const double* __restrict__ meanB, const double* __restrict__ bias,
+                         const double* __restrict__ sf, int sf_rows,
+                         const double* __restrict__ table, double* __restrict__ bm,
+                         double* __restrict__ disp) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t dist = (int64_t)col[i] - row[i];
+    for (int j = 0; j < J; ++j) {
+      const double s = sf[(sf_rows == 1 ? 0 : dist * J) + j];
+      bm[j * n + i] = h3d::sim_bm(j < J / 2 ? meanA[i] : meanB[i],
+                                  bias[(int64_t)row[i] * J + j],
+                                  bias[(int64_t)col[i] * J + j], s);
+      disp[j * n + i] = table[dist];
+    }
+  }
+}
+
+__global__ void k_poisson_quantile(int64_t n, const double* __restrict__ lambda,
+                                   const double* __restrict__ u, double* __restrict__ k,
+                                   int32_t* __restrict__ path) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int pth;
+    k[i] = h3d::poisson_quantile(lambda[i], u[i], &pth);
+    path[i] = pth;
   }
 }
 
@@ -359,6 +431,93 @@ H3DT_UNARY(exp_fast, kExpFast)
 H3DT_UNARY(log_fast_checked, kLogFastChecked)
 H3DT_UNARY(recip_fast, kRecipFast)
 H3DT_BINARY(div_fast, kDivFast)
+
+void h3dt_philox(int64_t n, const uint32_t* ctr, const uint32_t* key, uint32_t* out,
+                 double* u) {
+  Dev<uint32_t> dc(ctr, 4 * n), dk(key, 2 * n), dout_(nullptr, 4 * n);
+  Dev<double> du(nullptr, 2 * n);
+  hipLaunchKernelGGL(k_philox, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, dc.p, dk.p, dout_.p,
+                     du.p);
+  if (sync_ok()) {
+    dout_.to_host(out);
+    du.to_host(u);
+  }
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) {
+      out[4 * i] = out[4 * i + 1] = out[4 * i + 2] = out[4 * i + 3] = 0;
+      u[2 * i] = u[2 * i + 1] = NAN;
+    }
+}
+
+void h3dt_philox_uniform(int64_t n, const uint32_t* lo, const uint32_t* hi, double* u) {
+  Dev<uint32_t> dl(lo, n), dh(hi, n);
+  Dev<double> du(nullptr, n);
+  hipLaunchKernelGGL(k_philox_uniform, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, dl.p, dh.p,
+                     du.p);
+  if (sync_ok()) du.to_host(u);
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) u[i] = NAN;
+}
+
+int h3dt_nb_draw(int64_t n, const double* bm, const double* disp, const double* u1,
+                 const double* u2, double* lambda, int32_t* k, int32_t* path) {
+  Dev<double> db(bm, n), dd(disp, n), d1(u1, n), d2(u2, n), dl(nullptr, n);
+  Dev<int32_t> dk(nullptr, n), dp(nullptr, n);
+  Dev<int> dst(nullptr, 1);
+  hipLaunchKernelGGL(k_nb_draw, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, db.p, dd.p, d1.p,
+                     d2.p, dl.p, dk.p, dp.p, dst.p);
+  int st = 0;
+  if (sync_ok()) {
+    dl.to_host(lambda);
+    dk.to_host(k);
+    dp.to_host(path);
+    dst.to_host(&st);
+  }
+  if (g_failed) {
+    for (int64_t i = 0; i < n; ++i) {
+      lambda[i] = NAN;
+      k[i] = -2;
+    }
+    return -2;
+  }
+  return st;
+}
+
+// (-1 and no launch for a row / col outside [0, n_bins) or a col - row
+// outside [0, D))
+int h3dt_sim_bm(int64_t n, int J, int n_bins, int D, const int32_t* row,
+                const int32_t* col, const double* meanA, const double* meanB,
+                const double* bias, const double* sf, int sf_rows, const double* table,
+                double* bm, double* disp) {
+  for (int64_t i = 0; i < n; ++i)
+    if (row[i] < 0 || row[i] >= n_bins || col[i] < row[i] || col[i] >= n_bins ||
+        col[i] - row[i] >= D)
+      return -1;
+  Dev<int32_t> dr(row, n), dc(col, n);
+  Dev<double> da(meanA, n), db(meanB, n), dbi(bias, (size_t)n_bins * J),
+      ds(sf, (size_t)(sf_rows == 1 ? 1 : D) * J), dt(table, D), dbm(nullptr, (size_t)n * J),
+      dd(nullptr, (size_t)n * J);
+  hipLaunchKernelGGL(k_sim_bm, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, J, dr.p, dc.p, da.p,
+                     db.p, dbi.p, ds.p, sf_rows, dt.p, dbm.p, dd.p);
+  if (!sync_ok()) return -2;
+  dbm.to_host(bm);
+  dd.to_host(disp);
+  return g_failed ? -2 : 0;
+}
+
+void h3dt_poisson_quantile(int64_t n, const double* lambda, const double* u, double* k,
+                           int32_t* path) {
+  Dev<double> dl(lambda, n), du(u, n), dk(nullptr, n);
+  Dev<int32_t> dp(nullptr, n);
+  hipLaunchKernelGGL(k_poisson_quantile, dim3(grid_of(n)), dim3(kBlock), 0, 0, n, dl.p, du.p,
+                     dk.p, dp.p);
+  if (sync_ok()) {
+    dk.to_host(k);
+    dp.to_host(path);
+  }
+  if (g_failed)
+    for (int64_t i = 0; i < n; ++i) k[i] = NAN;
+}
 
 void h3dt_igam_pq(int64_t n, const double* a, const double* x, int tail,
                   double* P, double* Q, double* fac) {

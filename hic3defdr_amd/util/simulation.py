@@ -4,6 +4,10 @@ Host code with the reference's random-number semantics -- the legacy global
 numpy stream, drawn in the reference's order (one ``np.random.choice`` for
 the cluster classes, then one ``negative_binomial`` array per replicate) --
 so a seeded simulation reproduces the reference's matrices count for count.
+
+``simulate_gpu`` beside it draws the same distribution on the GPU from a
+counter-based stream (h3d_simulate_dev): other counts, each a function of
+(seed, stream, replicate, pixel index) alone.
 """
 import numpy as np
 import scipy.ndimage as ndimage
@@ -97,5 +101,157 @@ def simulate(row, col, mean, disp_fn, bias, size_factors, clusters, beta=0.5,
             nb_n, nb_p = _nb_params(bm, var)
             x = np.random.negative_binomial(nb_n, nb_p)
             yield sparse.coo_matrix((x, (row, col)), shape=(n, n)).tocsr()
+
+    return classes, gen()
+
+
+def class_probabilities(p_diff):
+    """``simulate``'s class probabilities from its ``p_diff``, checked."""
+    p = [1 - p_diff] + [p_diff / 4] * 4 if isinstance(p_diff, float) \
+        else [1 - sum(p_diff)] + list(p_diff)
+    p = np.asarray(p, dtype=np.float64)
+    if p.shape != (len(CLASSES),) or not np.all(np.isfinite(p)) or \
+            np.any(p < 0):
+        raise ValueError('p_diff must be a float in [0, 1] or four '
+                         'probabilities summing to at most 1')
+    return p
+
+
+def class_rng(seed, stream):
+    """The generator of ``simulate_gpu``'s class labels: a legacy
+    ``RandomState`` seeded with ``[seed, stream]`` (a seed of 2^32 or more
+    as its low and high 32-bit words: ``[low, high, stream]``), private to
+    the call -- numpy's global stream is neither read nor advanced."""
+    from hic3defdr_amd._native import check_stream
+    seed, stream, _, _ = check_stream(seed, stream)
+    words = [seed] if seed < 2 ** 32 else [seed & 0xffffffff, seed >> 32]
+    return np.random.RandomState(words + [stream])
+
+
+def _simulate_gpu_args(row, col, mean, disp_fn, bias, size_factors, clusters,
+                       p_diff, trend, seed, stream):
+    """Every check of ``simulate_gpu`` that needs no device: the arrays as
+    the kernel takes them, restricted to the pixels with a positive mean."""
+    from hic3defdr_amd._native import check_stream
+    if trend == 'mean':
+        raise NotImplementedError(
+            "simulate_gpu draws with trend='dist' only (the dispersion "
+            "table is indexed by distance)")
+    if trend != 'dist':
+        raise ValueError("trend must be 'dist'")
+    seed, stream, _, _ = check_stream(seed, stream)
+    p = class_probabilities(p_diff)
+    row, col, mean = np.asarray(row), np.asarray(col), np.asarray(mean)
+    if row.ndim != 1 or row.dtype.kind not in 'iu' or \
+            col.dtype.kind not in 'iu' or col.shape != row.shape or \
+            mean.shape != row.shape:
+        raise ValueError('row, col (integer) and mean must be (n,)')
+    mean = mean.astype(np.float64)
+    bias = np.asarray(bias, dtype=np.float64)
+    if bias.ndim != 2 or not 1 <= bias.shape[1] <= 32:
+        raise ValueError('bias must be (n_bins, J) with 1 <= J <= 32')
+    n_bins, J = bias.shape
+    if n_bins >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 bins')
+    if not np.all(np.isfinite(mean)):
+        raise ValueError('mean is not finite')
+    pos = mean > 0
+    row, col, mean = row[pos], col[pos], mean[pos]
+    if len(row) == 0:
+        raise ValueError('no pixel has a positive mean')
+    if row.min() < 0 or col.max() >= n_bins or np.any(col < row):
+        raise ValueError('pixels must satisfy 0 <= row <= col < n_bins')
+    dr, dc = np.diff(row), np.diff(col)
+    if not np.all((dr > 0) | ((dr == 0) & (dc > 0))):
+        raise ValueError('pixels must be unique and in (row, col) order')
+    D = int((col - row).max()) + 1
+    sf = np.asarray(size_factors, dtype=np.float64)
+    if sf.shape == (J,):
+        pass
+    elif sf.ndim == 2 and sf.shape[1] == J and sf.shape[0] >= D:
+        sf = sf[:D]
+    else:
+        raise ValueError('size_factors must be (J,) or (D, J) with a row '
+                         'per distance up to %d' % (D - 1))
+    if not np.all(np.isfinite(sf)) or np.any(sf <= 0):
+        raise ValueError('size_factors must be positive and finite')
+    table = np.asarray(disp_fn(np.arange(D)), dtype=np.float64)
+    if table.shape != (D,):
+        raise ValueError('disp_fn must map (D,) distances to (D,) values')
+    if not np.all(np.isfinite(table)) or np.any(table <= 0):
+        raise ValueError('disp_fn must be positive and finite on every '
+                         'distance')
+    for cluster in clusters:
+        if len(cluster) == 0:
+            raise ValueError('empty cluster')
+    return (seed, stream, p, row, col, mean, np.ascontiguousarray(bias),
+            np.ascontiguousarray(sf), table)
+
+
+def simulate_gpu(row, col, mean, disp_fn, bias, size_factors, clusters,
+                 beta=0.5, p_diff=0.4, trend='dist', seed=None, stream=0,
+                 verbose=True, ctx=None):
+    """``simulate`` with the draws on the GPU from a counter-based stream
+    (h3d_simulate_dev): the same classes-then-generator
+    return, the same distribution, a different, documented random stream.
+
+    The class labels come from ``class_rng(seed, stream)``, the perturbed
+    means from the host ``perturb_cluster``. The count of replicate j at the
+    i-th pixel with a positive mean is a pure function of (seed, stream, j,
+    i). ``trend='mean'`` is not implemented; the dispersion is
+    ``disp_fn(np.arange(D))[col - row]``. Every argument is checked before a
+    device is touched; numpy's global stream is not used."""
+    seed, stream, p, row, col, mean, bias, sf, table = _simulate_gpu_args(
+        row, col, mean, disp_fn, bias, size_factors, clusters, p_diff, trend,
+        seed, stream)
+    eprint('  assigning cluster classes', skip=not verbose)
+    classes = class_rng(seed, stream).choice(CLASSES, size=len(clusters), p=p)
+    eprint('  perturbing clusters', skip=not verbose)
+    n = bias.shape[0]
+    mats = {c: sparse.coo_matrix((mean, (row, col)), shape=(n, n)).tocsr()
+            for c in 'AB'}
+    effects = {'up A': ('A', beta), 'down A': ('A', -beta),
+               'up B': ('B', beta), 'down B': ('B', -beta)}
+    for i, cluster in enumerate(clusters):
+        if classes[i] in effects:
+            which, eff = effects[classes[i]]
+            perturb_cluster(mats[which], cluster, eff)
+    indptr, indices = mats['A'].indptr.copy(), mats['A'].indices.copy()
+    means = {}
+    for c in 'AB':
+        m = mats.pop(c)
+        # the pixel order is already CSR order (checked above), so the
+        # replicates share one indptr / indices
+        assert np.array_equal(m.indptr, indptr) and \
+            np.array_equal(m.indices, col)
+        if not np.all(m.data > 0):
+            raise ValueError('a perturbed mean is not positive')
+        means[c] = m.data
+    eprint('  renaming cluster classes', skip=not verbose)
+    classes[(classes == 'up A') | (classes == 'down B')] = 'A'
+    classes[(classes == 'up B') | (classes == 'down A')] = 'B'
+    eprint('  biasing and simulating %i reps on the GPU' % bias.shape[1],
+           skip=not verbose)
+    import torch
+    from hic3defdr_amd import _native
+    ctx = ctx or _native.context()
+    dev = torch.device('cuda', ctx.device)
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+    counts, flags = ctx.simulate_dev(
+        up(row, np.int32), up(col, np.int32), up(means['A'], np.float64),
+        up(means['B'], np.float64), up(bias, np.float64),
+        up(sf, np.float64), up(table, np.float64), seed, stream)
+    if flags:
+        raise ValueError('a biased mean is not positive and finite, or a '
+                         'Poisson mean reached 2^31 (status %d)' % flags)
+    counts = counts.cpu().numpy()
+
+    def gen():
+        for j in range(counts.shape[0]):
+            yield sparse.csr_matrix((counts[j].astype(np.int64), indices,
+                                     indptr), shape=(n, n))
 
     return classes, gen()

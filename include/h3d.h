@@ -22,6 +22,10 @@
  *   h3d_nb_equalize / _dev <- util/scaled_nb.py:186-214 equalize
  *   h3d_nb_quantile_map    <- util/scaled_nb.py:217-275 q2qnbinom
  *   h3d_nb_logpmf          <- util/scaled_nb.py:12-33 logpmf
+ *   h3d_nb_sample / _dev   <- util/simulation.py:187-203 (the negative-binomial
+ *                              draw of one replicate; a counter-based stream)
+ *   h3d_simulate_dev       <- util/simulation.py:187-203, every replicate of a
+ *                              chromosome from the means, biases, size factors
  *   h3d_bh / _ctx / _dev   <- analysis/analysis.py:286-303 (lib5c
  *                              adjust_pvalues = BH)
  *   h3d_find_clusters      <- util/clusters.py:73-97 find_clusters (threshold /
@@ -422,6 +426,47 @@ int h3d_nb_quantile_map(h3d_ctx* ctx, const double* x, double* mu_in,
 /* scaled_nb.py:12-33 logpmf, elementwise over n values of k, m, phi. */
 int h3d_nb_logpmf(h3d_ctx* ctx, const double* k, const double* m,
                   const double* phi, int64_t n, double* out);
+
+/* ---- negative-binomial sampling (simulate on the GPU) -------------------- */
+
+/* The draws of util/simulation.py:84-99 (reference simulation.py:187-203:
+ * one np.random.negative_binomial array per replicate) from a counter-based
+ * stream instead of numpy's sequential one. The draw of a pixel is a pure
+ * function of (seed, stream, rep, pixel index): Philox4x32-10 with key =
+ * (seed low word, seed high word) and counter = {index low word, index high
+ * word, rep, stream} gives four words w0..w3; u1 = ((w1:w0 >> 12) + 1/2)
+ * 2^-52 and u2 the same of w3:w2; the Poisson mean is lambda = bm disp
+ * gammaincinv(1 / disp, u1) (bm disp gammainccinv(1 / disp, 1 - u1) above
+ * 1/2) and the count the smallest k with pdtr(k, lambda) >= u2 (DESIGN.md §1
+ * F9). The pixel index of element i is pixel0 + i, so a slice of a pixel list
+ * drawn with its offset equals the slice of the whole list's draws. bm or
+ * disp not positive finite, or lambda not below 2^31: count -1 and
+ * H3D_FLAG_BADIN in *flags (may be NULL); the return code stays 0. */
+
+/* simulation.py:187-203 for one replicate whose biased means bm (n) and
+ * dispersions disp (n) the caller formed: counts (n) int32 and, when lambda
+ * is not NULL, the gamma stage's lambda (n). */
+int h3d_nb_sample(h3d_ctx* ctx, const double* bm, const double* disp, int64_t n,
+                  uint64_t seed, uint32_t stream, uint32_t rep, int64_t pixel0,
+                  int32_t* counts, double* lambda, int* flags);
+int h3d_nb_sample_dev(h3d_ctx* ctx, const double* d_bm, const double* d_disp,
+                      int64_t n, uint64_t seed, uint32_t stream, uint32_t rep,
+                      int64_t pixel0, int32_t* d_counts, double* d_lambda,
+                      int* flags);
+
+/* simulation.py:187-203 for all J replicates (1 <= J <= 32) of one
+ * chromosome, fused: replicate j takes meanA (j < J / 2) or meanB, bm = mean
+ * x (bias[row, j] x bias[col, j] x sf) with bias (n_bins, J) and sf =
+ * d_sf[j] (sf_rows = 1) or d_sf[dist x J + j] (sf_rows = D), dist = col - row,
+ * disp = d_table[dist] (D entries), rep = j. d_counts: (J, n) int32, one
+ * contiguous plane per replicate. A pixel with row or col outside [0, n_bins)
+ * or dist outside [0, D) gets -1 and H3D_FLAG_BADIN. */
+int h3d_simulate_dev(h3d_ctx* ctx, const int32_t* d_row, const int32_t* d_col,
+                     const double* d_meanA, const double* d_meanB,
+                     const double* d_bias, const double* d_sf, int sf_rows,
+                     const double* d_table, int D, int64_t n, int J, int n_bins,
+                     uint64_t seed, uint32_t stream, int64_t pixel0,
+                     int32_t* d_counts, int* flags);
 
 /* ---- bh ---------------------------------------------------------------- */
 
