@@ -47,6 +47,9 @@ EXPORTS = [
     'h3d_pixel_membership', 'h3d_pixel_membership_dev', 'h3d_roc_curve',
     'h3d_roc_curve_dev', 'h3d_order_stats', 'h3d_bin_fractions',
     'h3d_nb_sample', 'h3d_nb_sample_dev', 'h3d_simulate_dev',
+    'h3d_label_components', 'h3d_label_components_dev',
+    'h3d_threshold_classes_dev', 'h3d_argmax_classes_dev',
+    'h3d_cluster_lists', 'h3d_cluster_lists_dev',
 ]
 
 
@@ -69,6 +72,20 @@ class H3DError(RuntimeError):
 
 
 H3D_EINPUT = -5
+H3D_FLAG_BADIN = 16
+# the calls as connected components (h3d_label_components): the class byte of
+# "no pixel", the largest class count and pixel count, the input rule
+CLS_ABSENT = 255
+CCL_MAX_CLASSES = 254
+CCL_MAX_N = 2 ** 31 - 2
+BAD_PIXELS = ('pixels must be distinct, in (row, col) order, with '
+              'coordinates in [0, 2^31)')
+
+
+def check_class_count(C):
+    if not 1 <= int(C) <= CCL_MAX_CLASSES:
+        raise ValueError('between 1 and %d classes, got %d'
+                         % (CCL_MAX_CLASSES, C))
 
 
 _P = ctypes.c_void_p
@@ -228,6 +245,16 @@ def load_library(path=None):
             'h3d_order_stats': (_I, [_P, _P, _I64, _P, _I, _P, _P]),
             'h3d_bin_fractions': (_I, [_P, _P, _P, _I64, _P, _P, _I, _D, _P,
                                        _P]),
+            'h3d_label_components': (_I, [_P, _P, _P, _P, _I64, _I, _P, _P,
+                                          _P]),
+            'h3d_label_components_dev': (_I, [_P, _P, _P, _P, _I64, _I, _P,
+                                              _P, _P]),
+            'h3d_threshold_classes_dev': (_I, [_P, _P, _I64, _D, _P]),
+            'h3d_argmax_classes_dev': (_I, [_P, _P, _I64, _I, _P, _P]),
+            'h3d_cluster_lists': (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64,
+                                       _P, _P, _P, _P, _P, _P, _P]),
+            'h3d_cluster_lists_dev': (_I, [_P, _P, _P, _P, _P, _I64, _I64,
+                                           _I64, _P, _P, _P, _P, _P, _P, _P]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -1118,6 +1145,142 @@ class Context(object):
             _P(prow.data_ptr()), _P(pcol.data_ptr()), prow.numel(),
             _P(out.data_ptr())), 'h3d_pixel_membership_dev')
         return out.to(torch.bool)
+
+    # -- the calls as connected components (util/clusters.py) -----------------
+    def label_components(self, row, col, cls, connectivity=1):
+        """(label int32 (n), n_clusters) of h3d_label_components: int64 host
+        pixels in (row, col) order, ``cls`` a class byte per pixel (255 = no
+        pixel). ValueError where the library reports H3D_FLAG_BADIN."""
+        row, col = _c(row, np.int64), _c(col, np.int64)
+        cls = _c(cls, np.uint8)
+        if row.ndim != 1 or col.shape != row.shape or cls.shape != row.shape:
+            raise ValueError('row, col and cls must be (n,)')
+        label = np.empty(len(row), dtype=np.int32)
+        nc, fl = _I64(0), _I(0)
+        _check(self.lib.h3d_label_components(
+            self.handle, _ptr(row), _ptr(col), _ptr(cls), len(row),
+            int(connectivity), _ptr(label), ctypes.byref(nc),
+            ctypes.byref(fl)), 'h3d_label_components')
+        if fl.value & H3D_FLAG_BADIN:
+            raise ValueError(BAD_PIXELS)
+        return label, nc.value
+
+    def label_components_dev(self, row, col, cls, connectivity=1):
+        """label_components on torch tensors of this ctx's device (row, col
+        int64, cls uint8); returns (int32 label tensor, n_clusters)."""
+        import torch
+        if row.dtype != torch.int64 or col.dtype != torch.int64 or \
+                cls.dtype != torch.uint8:
+            raise ValueError('row, col must be int64 and cls uint8')
+        if row.dim() != 1 or col.shape != row.shape or cls.shape != row.shape:
+            raise ValueError('row, col and cls must be (n,)')
+        row, col, cls = row.contiguous(), col.contiguous(), cls.contiguous()
+        label = torch.empty(row.numel(), dtype=torch.int32, device=row.device)
+        nc, fl = _I64(0), _I(0)
+        torch.cuda.current_stream(row.device).synchronize()
+        _check(self.lib.h3d_label_components_dev(
+            self.handle, _P(row.data_ptr()), _P(col.data_ptr()),
+            _P(cls.data_ptr()), row.numel(), int(connectivity),
+            _P(label.data_ptr()), ctypes.byref(nc), ctypes.byref(fl)),
+            'h3d_label_components_dev')
+        if fl.value & H3D_FLAG_BADIN:
+            raise ValueError(BAD_PIXELS)
+        return label, nc.value
+
+    def threshold_classes_dev(self, q, fdr):
+        """uint8 class tensor of float64 q-values on this ctx's device: 0
+        where q < fdr, 1 where q >= fdr, 255 for NaN
+        (h3d_threshold_classes_dev)."""
+        import torch
+        if q.dtype != torch.float64 or q.dim() != 1:
+            raise ValueError('q must be float64 (n,)')
+        q = q.contiguous()
+        cls = torch.empty(q.numel(), dtype=torch.uint8, device=q.device)
+        torch.cuda.current_stream(q.device).synchronize()
+        _check(self.lib.h3d_threshold_classes_dev(
+            self.handle, _P(q.data_ptr()), q.numel(), float(fdr),
+            _P(cls.data_ptr())), 'h3d_threshold_classes_dev')
+        return cls
+
+    def argmax_classes_dev(self, value, member):
+        """uint8 class tensor: np.argmax of each row of ``value`` (n, C)
+        float64 where ``member`` (n) uint8 / bool is set, 255 elsewhere
+        (h3d_argmax_classes_dev)."""
+        import torch
+        if value.dtype != torch.float64 or value.dim() != 2:
+            raise ValueError('value must be float64 (n, C)')
+        if member.dtype == torch.bool:
+            member = member.to(torch.uint8)
+        if member.dtype != torch.uint8 or member.shape != value.shape[:1]:
+            raise ValueError('member must be uint8 / bool (n,)')
+        check_class_count(value.shape[1])
+        value, member = value.contiguous(), member.contiguous()
+        n = value.shape[0]
+        cls = torch.empty(n, dtype=torch.uint8, device=value.device)
+        torch.cuda.current_stream(value.device).synchronize()
+        _check(self.lib.h3d_argmax_classes_dev(
+            self.handle, _P(value.data_ptr()), n, int(value.shape[1]),
+            _P(member.data_ptr()), _P(cls.data_ptr())),
+            'h3d_argmax_classes_dev')
+        return cls
+
+    CLUSTER_FIELDS = ('size', 'cls_of', 'bounds', 'members', 'starts')
+
+    def cluster_lists(self, label, cls, row, col, n_clusters, min_size=1):
+        """dict of CLUSTER_FIELDS of h3d_cluster_lists on host arrays: size
+        (n_clusters) int32, cls_of (n_clusters) uint8, bounds (4, n_clusters)
+        int32 (min row, max row, min col, max col), and of the clusters with
+        size >= min_size members (int32 pixel indices) and starts (int64)."""
+        label, cls = _c(label, np.int32), _c(cls, np.uint8)
+        row, col = _c(row, np.int64), _c(col, np.int64)
+        n, nc = len(label), int(n_clusters)
+        if label.ndim != 1 or any(a.shape != label.shape
+                                  for a in (cls, row, col)):
+            raise ValueError('label, cls, row and col must be (n,)')
+        size = np.empty(nc, dtype=np.int32)
+        cls_of = np.empty(nc, dtype=np.uint8)
+        bounds = np.empty((4, nc), dtype=np.int32)
+        members = np.empty(n, dtype=np.int32)
+        starts = np.zeros(nc + 1, dtype=np.int64)
+        nk, nm = _I64(0), _I64(0)
+        _check(self.lib.h3d_cluster_lists(
+            self.handle, _ptr(label), _ptr(cls), _ptr(row), _ptr(col), n, nc,
+            int(min_size), _ptr(size), _ptr(cls_of), _ptr(bounds),
+            _ptr(members), _ptr(starts), ctypes.byref(nk), ctypes.byref(nm)),
+            'h3d_cluster_lists')
+        return dict(size=size, cls_of=cls_of, bounds=bounds,
+                    members=members[:nm.value].copy(),
+                    starts=starts[:nk.value + 1].copy())
+
+    def cluster_lists_dev(self, label, cls, row, col, n_clusters, min_size=1):
+        """cluster_lists on torch tensors of this ctx's device (label int32,
+        cls uint8, row / col int64); returns a dict of tensors."""
+        import torch
+        if label.dtype != torch.int32 or cls.dtype != torch.uint8 or \
+                row.dtype != torch.int64 or col.dtype != torch.int64:
+            raise ValueError('label int32, cls uint8, row / col int64')
+        if label.dim() != 1 or any(t.shape != label.shape
+                                   for t in (cls, row, col)):
+            raise ValueError('label, cls, row and col must be (n,)')
+        label, cls = label.contiguous(), cls.contiguous()
+        row, col = row.contiguous(), col.contiguous()
+        n, nc, dev = label.numel(), int(n_clusters), label.device
+        size = torch.empty(nc, dtype=torch.int32, device=dev)
+        cls_of = torch.empty(nc, dtype=torch.uint8, device=dev)
+        bounds = torch.empty((4, nc), dtype=torch.int32, device=dev)
+        members = torch.empty(n, dtype=torch.int32, device=dev)
+        starts = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
+        nk, nm = _I64(0), _I64(0)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self.lib.h3d_cluster_lists_dev(
+            self.handle, _P(label.data_ptr()), _P(cls.data_ptr()),
+            _P(row.data_ptr()), _P(col.data_ptr()), n, nc, int(min_size),
+            _P(size.data_ptr()), _P(cls_of.data_ptr()),
+            _P(bounds.data_ptr()), _P(members.data_ptr()),
+            _P(starts.data_ptr()), ctypes.byref(nk), ctypes.byref(nm)),
+            'h3d_cluster_lists_dev')
+        return dict(size=size, cls_of=cls_of, bounds=bounds,
+                    members=members[:nm.value], starts=starts[:nk.value + 1])
 
     ROC_FIELDS = ('fdr', 'fpr', 'tpr', 'thresh', 'fps', 'tps')
 

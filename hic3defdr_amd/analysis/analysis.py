@@ -33,12 +33,14 @@ from hic3defdr_amd import _native, numa, parallel
 from hic3defdr_amd.analysis.core import DispFn
 from hic3defdr_amd.analysis.d2h import small_to_host, to_host_async
 from hic3defdr_amd.analysis.resident import bias_stamps
-from hic3defdr_amd.util.classification import classify_clusters
+from hic3defdr_amd.util.classification import classify_clusters, \
+    classify_clusters_gpu
 from hic3defdr_amd.util.cluster_table import ClusterTable
 from hic3defdr_amd.util.clusters import (load_cluster_list,
                                          load_cluster_pixels,
                                          pixel_membership, save_clusters)
-from hic3defdr_amd.util.thresholding import threshold_clusters
+from hic3defdr_amd.util.thresholding import threshold_clusters, \
+    threshold_clusters_gpu
 from hic3defdr_amd.util.printing import eprint
 
 NATIVE_NORMS = tuple(_native.H3D_NORM)
@@ -603,18 +605,29 @@ class AnalyzingHiC3DeFDR(object):
     def _chroms_for(self, chrom):
         return self.chroms if chrom is None else [chrom]
 
-    def threshold(self, chrom=None, fdr=0.05, cluster_size=3, n_threads=-1):
+    def threshold(self, chrom=None, fdr=0.05, cluster_size=3, n_threads=-1,
+                  gpu=False):
         """Reference ``analysis.py:366-431``: sig / insig clusters per FDR
         and cluster size -> ``sig_<fdr>_<size>_<chrom>.json`` (+ ``.tsv``
-        when ``res`` is set), same for ``insig``."""
+        when ``res`` is set), same for ``insig``.
+
+        ``gpu=True``: the clusters are labelled on the GPU
+        (``threshold_clusters_gpu``; a chromosome's pixels and q-values are
+        uploaded once for all the FDRs). The files, their formats and the
+        clusters as sets of pixels are the same; their order is canonical
+        instead of the reference's -- clusters by their first pixel, pixels
+        in (row, col) order (deviation 10)."""
         fdrs = list(fdr) if hasattr(fdr, '__len__') else [fdr]
         sizes = list(cluster_size) if hasattr(cluster_size, '__len__') \
             else [cluster_size]
         for ch in self._chroms_for(chrom):
             eprint('thresholding and clustering chrom %s' % ch)
             row, col, q = self.load_data('qvalues', ch, coo=True)
-            for f in fdrs:
-                sig, insig = threshold_clusters(q, row, col, f)
+            if gpu:
+                pairs = threshold_clusters_gpu(q, row, col, fdrs, sizes)
+            for k, f in enumerate(fdrs):
+                sig, insig = pairs[k] if gpu else \
+                    threshold_clusters(q, row, col, f)
                 for s in sizes:
                     for kind, cl in (('sig', sig), ('insig', insig)):
                         kept = cl.size_filter(s)
@@ -625,10 +638,16 @@ class AnalyzingHiC3DeFDR(object):
                             ClusterTable.from_clusters(kept, ch, self.res)\
                                 .to_tsv(out.replace('.json', '.tsv'))
 
-    def classify(self, chrom=None, fdr=0.05, cluster_size=3, n_threads=-1):
+    def classify(self, chrom=None, fdr=0.05, cluster_size=3, n_threads=-1,
+                 gpu=False):
         """Reference ``analysis.py:433-486``: significant pixels take the
         condition of their largest alt-model mean and are re-clustered per
-        condition -> ``<cond>_<fdr>_<size>_<chrom>.json`` (+ ``.tsv``)."""
+        condition -> ``<cond>_<fdr>_<size>_<chrom>.json`` (+ ``.tsv``).
+
+        ``gpu=True``: membership, the argmax and the re-clustering run on
+        the GPU (``classify_clusters_gpu``), and a missing ``sig`` file is
+        written by ``threshold(gpu=True)``; the same files and sets of
+        pixels in canonical order (see ``threshold``)."""
         fdrs = list(fdr) if hasattr(fdr, '__len__') else [fdr]
         sizes = list(cluster_size) if hasattr(cluster_size, '__len__') \
             else [cluster_size]
@@ -643,9 +662,11 @@ class AnalyzingHiC3DeFDR(object):
                 for s in sizes:
                     infile = '%s/sig_%g_%i_%s.json' % (self.outdir, f, s, ch)
                     if not os.path.isfile(infile):
-                        self.threshold(chrom=ch, fdr=f, cluster_size=s)
+                        self.threshold(chrom=ch, fdr=f, cluster_size=s,
+                                       gpu=gpu)
                     sig = load_cluster_list(infile)
-                    per_class = classify_clusters(row, col, mu_hat_alt, sig)
+                    per_class = (classify_clusters_gpu if gpu else
+                                 classify_clusters)(row, col, mu_hat_alt, sig)
                     for i, cl in enumerate(per_class):
                         out = '%s/%s_%g_%i_%s.json' % (
                             self.outdir, self.design.columns[i], f, s, ch)
@@ -654,10 +675,12 @@ class AnalyzingHiC3DeFDR(object):
                             ClusterTable.from_clusters(cl, ch, self.res)\
                                 .to_tsv(out.replace('.json', '.tsv'))
 
-    def collect(self, fdr=0.05, cluster_size=3, n_threads=-1):
+    def collect(self, fdr=0.05, cluster_size=3, n_threads=-1, gpu=False):
         """Reference ``analysis.py:488-572``: every chromosome's insig
         ("constitutive") and per-condition tables -> one sorted
-        ``results_<fdr>_<size>.tsv`` with a ``classification`` column."""
+        ``results_<fdr>_<size>.tsv`` with a ``classification`` column.
+        ``gpu=True`` is passed to the ``threshold`` / ``classify`` steps this
+        triggers; the text formatting stays on the host."""
         if self.res is None:
             raise ValueError(
                 'the collect() step can only be run if the res kwarg was '
@@ -677,10 +700,10 @@ class AnalyzingHiC3DeFDR(object):
                     return pattern.replace('<class>', k).replace('<chrom>', ch)
                 if not all(os.path.isfile(path('insig', ch))
                            for ch in self.chroms):
-                    self.threshold(fdr=f, cluster_size=s)
+                    self.threshold(fdr=f, cluster_size=s, gpu=gpu)
                 if not all(os.path.isfile(path(c, ch)) for c in conds
                            for ch in self.chroms):
-                    self.classify(fdr=f, cluster_size=s)
+                    self.classify(fdr=f, cluster_size=s, gpu=gpu)
                 tables = []
                 for ch in self.chroms:
                     tables.append(ClusterTable.read_tsv(path('insig', ch))

@@ -51,7 +51,7 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
                ('h3d_nb.hip', 'hipcc'), ('h3d_diag.hip', 'hipcc'),
                ('h3d_eval.hip', 'hipcc'), ('h3d_sim.hip', 'hipcc'),
-               ('h3d_ctx.hip', 'hipcc'),
+               ('h3d_clusters.hip', 'hipcc'), ('h3d_ctx.hip', 'hipcc'),
                ('h3d_cub_sort_idx.hip', 'hipcc'), ('h3d_cub_sort_int.hip', 'hipcc'),
                ('h3d_cub_sort_f64.hip', 'hipcc'), ('h3d_cub_scan.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]

@@ -1,13 +1,14 @@
 // Host build of the device numerics, for CPU unit tests ONLY.
 //
 // The same headers the gfx950 kernels include (h3d_special.h, h3d_model.h,
-// h3d_philox.h, h3d_sample.h)
+// h3d_philox.h, h3d_sample.h, h3d_ccl.h)
 // compiled with g++ and exported over a flat C ABI so tests/ can check them
 // against scipy / the oracle without a GPU. The product never loads this
 // library (hic3defdr_amd loads libh3d.so and fails loudly without it).
 #include <cstdint>
 #include <vector>
 
+#include "h3d_ccl.h"
 #include "h3d_model.h"
 #include "h3d_philox.h"
 #include "h3d_sample.h"
@@ -337,6 +338,72 @@ int h3dt_disp_rounds(int64_t n, int R, int C, const int32_t* raw,
     if (flags_out) flags_out[s] = st[s].flags;
   }
   return 0;
+}
+
+// h3d_label_components (h3d_clusters.hip) with a serial union-find in place
+// of the CAS: the same input check, run-head / run-tail predicates and link
+// enumeration (h3d_ccl.h), run ids from a serial count, labels by first
+// pixel. Returns 16 (H3D_FLAG_BADIN; label all -1, *n_clusters 0) where the
+// input breaks the (row, col) rule, -1 for a bad argument, 0 otherwise.
+int h3dt_ccl_labels(const int64_t* row, const int64_t* col, const uint8_t* cls, int64_t n,
+                    int connectivity, int32_t* label, int64_t* n_clusters) {
+  using namespace h3dccl;
+  if (n < 0 || n > (((int64_t)1 << 31) - 2) || !n_clusters) return -1;
+  if (connectivity != 1 && connectivity != 2) return -1;
+  *n_clusters = 0;
+  if (n == 0) return 0;
+  if (!row || !col || !cls || !label) return -1;
+  bool bad = false;
+  for (int64_t i = 0; i < n; ++i) {
+    bad = bad || bad_pixel(row, col, i);
+    label[i] = -1;
+  }
+  if (bad) return 16;
+  std::vector<int32_t> incl((size_t)n), first;
+  std::vector<uint64_t> key0, key1;
+  std::vector<uint8_t> rcls;
+  int32_t count = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (run_head(row, col, cls, i)) {
+      ++count;
+      first.push_back((int32_t)i);
+      key0.push_back(pixel_key(row[i], col[i]));
+      key1.push_back(0);
+      rcls.push_back(cls[i]);
+    }
+    incl[i] = count;
+    if (run_tail(row, col, cls, i, n)) key1[count - 1] = pixel_key(row[i], col[i]);
+  }
+  if (count == 0) return 0;
+  std::vector<int32_t> parent((size_t)count);
+  for (int32_t r = 0; r < count; ++r) parent[r] = r;
+  auto find = [&](int32_t x) {
+    while (parent[x] != x) x = parent[x] = parent[parent[x]];
+    return x;
+  };
+  const Runs runs{first.data(), key0.data(), key1.data(), rcls.data(), count};
+  for (int32_t r = 0; r < count; ++r)
+    for_each_link(runs, r, connectivity, [&](int32_t a, int32_t b) {
+      a = find(a), b = find(b);
+      if (a != b) parent[a > b ? a : b] = a > b ? b : a;  // the smaller id stays the root
+    });
+  std::vector<int32_t> rank((size_t)count);
+  int32_t n_roots = 0;
+  for (int32_t r = 0; r < count; ++r) rank[r] = find(r) == r ? n_roots++ : -1;
+  for (int64_t i = 0; i < n; ++i)
+    if (cls[i] != kAbsent) label[i] = rank[find(incl[i] - 1)];
+  *n_clusters = n_roots;
+  return 0;
+}
+
+// q_class / argmax_class of h3d_ccl.h over n pixels (value (n, C) row-major)
+void h3dt_q_class(int64_t n, const double* q, double fdr, uint8_t* cls) {
+  for (int64_t i = 0; i < n; ++i) cls[i] = h3dccl::q_class(q[i], fdr);
+}
+void h3dt_argmax_class(int64_t n, int C, const double* value, const uint8_t* member,
+                       uint8_t* cls) {
+  for (int64_t i = 0; i < n; ++i)
+    cls[i] = member[i] ? h3dccl::argmax_class(value + i * C, C) : h3dccl::kAbsent;
 }
 
 }  // extern "C"

@@ -15,6 +15,12 @@ Two forms:
 
 Clustering itself is ``h3d_find_clusters`` in libh3d (host C++ restatement of
 the DirectedDisjointSet, clusters.py:15-97).
+
+``ClusterList.find_gpu`` / ``find_clusters_gpu`` give the same clusters as
+sets of pixels from the GPU (h3d_label_components, a run-based connected-
+component labelling) in a canonical order instead of the reference's:
+clusters by their first pixel in (row, col) order, pixels inside a cluster in
+(row, col) order (deviation 10).
 """
 import json
 import re
@@ -28,11 +34,15 @@ class ClusterList(object):
     """Cluster k = pixels ``(row[m], col[m])`` for
     ``m in members[starts[k]:starts[k + 1]]``."""
 
-    def __init__(self, row, col, members, starts):
+    def __init__(self, row, col, members, starts, bounds=None):
         self.row = np.asarray(row, dtype=np.int64)
         self.col = np.asarray(col, dtype=np.int64)
         self.members = np.asarray(members, dtype=np.int64)
         self.starts = np.asarray(starts, dtype=np.int64)
+        # (4, len(self)) min row, max row, min col, max col when the clusters
+        # came with them (find_gpu computes them on the device), else None
+        self._bounds = None if bounds is None else \
+            np.asarray(bounds, dtype=np.int64).reshape(4, len(self.starts) - 1)
 
     @classmethod
     def empty(cls):
@@ -69,6 +79,19 @@ class ClusterList(object):
         return cls(row, col, order, starts)
 
     @classmethod
+    def find_gpu(cls, row, col, connectivity=1):
+        """The clusters of ``find`` as sets of pixels, labelled on the GPU
+        (h3d_label_components), in canonical order: clusters by their first
+        pixel, pixels in (row, col) order. The pixels must be distinct, in
+        (row, col) order, with coordinates in [0, 2^31) (ValueError
+        otherwise, before a device is touched). There is no CPU fallback."""
+        row, col = check_pixels(row, col, connectivity)
+        if len(row) == 0:
+            return cls.empty()
+        return components_gpu(row, col, np.zeros(len(row), dtype=np.uint8),
+                              1, connectivity=connectivity)[0]
+
+    @classmethod
     def from_sets(cls, clusters):
         """From the reference form (list of iterables of (i, j))."""
         rows, cols, sizes = [], [], []
@@ -97,7 +120,9 @@ class ClusterList(object):
         idx = np.repeat(keep, self.sizes())
         starts = np.zeros(len(sz) + 1, dtype=np.int64)
         np.cumsum(sz, out=starts[1:])
-        return ClusterList(self.row, self.col, self.members[idx], starts)
+        return ClusterList(self.row, self.col, self.members[idx], starts,
+                           None if self._bounds is None
+                           else self._bounds[:, keep])
 
     def size_filter(self, cluster_size):
         """thresholding.py:44-61: keep clusters with >= cluster_size pixels."""
@@ -112,6 +137,8 @@ class ClusterList(object):
         if not len(self):
             z = np.zeros(0, dtype=np.int64)
             return z, z, z, z
+        if self._bounds is not None:
+            return tuple(self._bounds)
         r, c = self.pixels()
         s = self.starts[:-1]
         return (np.minimum.reduceat(r, s), np.maximum.reduceat(r, s),
@@ -148,6 +175,80 @@ def find_clusters(sig_points, connectivity=1):
     import scipy.sparse as sparse
     m = sparse.coo_matrix(sig_points)
     return ClusterList.find(m.row, m.col, connectivity).to_sets()
+
+
+def check_pixels(row, col, connectivity=1):
+    """The input rule of the GPU labelling, checked on the host before a
+    device is touched: integer (n,) arrays of one length, n <= 2^31 - 2,
+    coordinates in [0, 2^31), strictly increasing in (row, col) order (so
+    distinct); connectivity 1 or 2. Returns (row, col) as int64."""
+    row, col = np.asarray(row), np.asarray(col)
+    for a, what in ((row, 'row'), (col, 'col')):
+        if a.dtype.kind not in 'iu':
+            raise TypeError('%s must be integers, not %s' % (what, a.dtype))
+        if a.ndim != 1:
+            raise ValueError('%s must have 1 dimension' % what)
+    if row.shape != col.shape:
+        raise ValueError('row and col must have one length')
+    if isinstance(connectivity, bool) or connectivity not in (1, 2):
+        raise ValueError('connectivity must be 1 or 2, got %r'
+                         % (connectivity,))
+    if len(row) > _native.CCL_MAX_N:
+        raise ValueError('at most 2^31 - 2 pixels')
+    if len(row):
+        if min(row.min(), col.min()) < 0 or \
+                max(row.max(), col.max()) >= 2 ** 31:
+            raise ValueError(_native.BAD_PIXELS)
+        dr = row[1:] > row[:-1]
+        same = row[1:] == row[:-1]
+        if not np.all(dr | (same & (col[1:] > col[:-1]))):
+            raise ValueError(_native.BAD_PIXELS)
+    return row.astype(np.int64, copy=False), col.astype(np.int64, copy=False)
+
+
+def components_dev(ctx, row, col, t_row, t_col, t_cls, n_classes,
+                   connectivity=1, min_size=1):
+    """One ``ClusterList`` per class 0 .. n_classes - 1 from the device:
+    ``t_row`` / ``t_col`` (int64) and the class bytes ``t_cls`` (uint8, 255 =
+    no pixel) are torch tensors of ``ctx``'s device holding the host pixels
+    ``row`` / ``col``. Clusters below ``min_size`` pixels are not listed. The
+    lists share ``row`` / ``col`` and carry the device's bounding boxes."""
+    label, nc = ctx.label_components_dev(t_row, t_col, t_cls, connectivity)
+    out = ctx.cluster_lists_dev(label, t_cls, t_row, t_col, nc, min_size)
+    kept = out['size'].cpu().numpy() >= max(int(min_size), 1)
+    cls_of = out['cls_of'].cpu().numpy()[kept]
+    whole = ClusterList(row, col, out['members'].cpu().numpy(),
+                        out['starts'].cpu().numpy(),
+                        out['bounds'].cpu().numpy()[:, kept])
+    return [whole.select(cls_of == k) for k in range(n_classes)]
+
+
+def components_gpu(row, col, cls, n_classes, connectivity=1, min_size=1,
+                   ctx=None):
+    """``components_dev`` for host arrays (checked by ``check_pixels``)."""
+    import torch
+    ctx = ctx or _native.context()
+    dev = torch.device('cuda', ctx.device)
+    t_row = torch.from_numpy(np.ascontiguousarray(row)).to(dev)
+    t_col = torch.from_numpy(np.ascontiguousarray(col)).to(dev)
+    t_cls = torch.from_numpy(np.ascontiguousarray(cls, dtype=np.uint8)).to(dev)
+    return components_dev(ctx, row, col, t_row, t_col, t_cls, n_classes,
+                          connectivity, min_size)
+
+
+def find_clusters_gpu(sig_points, connectivity=1):
+    """``find_clusters`` on the GPU: a boolean matrix (scipy sparse or
+    dense) -> the canonical CSR pixel order -> ``ClusterList.find_gpu``; a
+    list of sets of tuples, clusters ordered by their first pixel."""
+    import scipy.sparse as sparse
+    m = sparse.csr_matrix(sig_points, dtype=bool)
+    m.sum_duplicates()
+    m.eliminate_zeros()
+    m.sort_indices()
+    m = m.tocoo()
+    return ClusterList.find_gpu(m.row.astype(np.int64),
+                                m.col.astype(np.int64),
+                                connectivity).to_sets()
 
 
 def load_clusters(infile):

@@ -30,6 +30,11 @@
  *                              adjust_pvalues = BH)
  *   h3d_find_clusters      <- util/clusters.py:73-97 find_clusters (threshold /
  *                              classify, analysis.py:366-486)
+ *   h3d_label_components / _dev, h3d_cluster_lists / _dev
+ *                          <- util/clusters.py:69-97 as connected components
+ *                              (threshold / classify with gpu=True)
+ *   h3d_threshold_classes_dev <- util/thresholding.py:7-41 (q < fdr, q >= fdr)
+ *   h3d_argmax_classes_dev <- util/classification.py:7-49 (np.argmax)
  *   h3d_format_clusters    <- util/clusters.py:129-130 save_clusters text,
  *                              util/cluster_table.py:67 "cluster" column
  *   h3d_lrt_poisson        <- analysis/alternatives.py:17-42 poisson_lrt
@@ -530,6 +535,70 @@ int h3d_format_clusters(const int64_t* row, const int64_t* col,
                         const int64_t* order, const int64_t* starts,
                         int64_t n_clusters, char* buf, int64_t cap,
                         int64_t* ends, int64_t* len);
+
+/* ---- threshold / classify on the GPU ------------------------------------- */
+
+/* The calls as connected components. The pixels (row[i], col[i]) come in the
+ * outdir layout: strictly increasing in (row, col) order (so distinct),
+ * coordinates in [0, 2^31), n <= 2^31 - 2; cls (n) is a class byte per pixel,
+ * 255 = no pixel. Two pixels connect when they are adjacent (connectivity 1 =
+ * an edge, 2 = an edge or a corner) and of equal class, so every class is
+ * clustered in the one pass. The partition is that of find_clusters
+ * (clusters.py:69-97) per class: its directed bookkeeping orders the output,
+ * never the membership. The ORDER is not the reference's but canonical:
+ * label[i] (int32; -1 for a class-255 pixel) numbers the clusters by their
+ * first pixel in (row, col) order, 0 .. *n_clusters - 1. The input rule is
+ * checked once per call on the device; an input that breaks it sets
+ * H3D_FLAG_BADIN in *flags beside rc 0 (label all -1, *n_clusters 0).
+ * H3D_EARG for a connectivity other than 1 or 2. Labels depend on nothing but
+ * the input (run-based union-find with the smallest id as representative;
+ * integer atomics only). _dev: row, col, cls and label are device pointers;
+ * n_clusters and flags are host words either way. Synchronous. */
+int h3d_label_components(h3d_ctx* ctx, const int64_t* row, const int64_t* col,
+                         const uint8_t* cls, int64_t n, int connectivity,
+                         int32_t* label, int64_t* n_clusters, int* flags);
+int h3d_label_components_dev(h3d_ctx* ctx, const int64_t* d_row,
+                             const int64_t* d_col, const uint8_t* d_cls,
+                             int64_t n, int connectivity, int32_t* d_label,
+                             int64_t* n_clusters, int* flags);
+
+/* The class byte of threshold (thresholding.py:7-41): d_cls[i] = 0 where
+ * d_q[i] < fdr (sig), 1 where d_q[i] >= fdr (insig), 255 for a NaN (in
+ * neither). Device pointers; synchronous. */
+int h3d_threshold_classes_dev(h3d_ctx* ctx, const double* d_q, int64_t n,
+                              double fdr, uint8_t* d_cls);
+
+/* The class byte of classify (classification.py:7-49): for a pixel with
+ * d_member[i] != 0, np.argmax of its row of d_value (n, C) row-major -- the
+ * first maximum, and the first NaN wins; 255 for the others. 1 <= C <= 254
+ * (H3D_EARG otherwise). Device pointers; synchronous. */
+int h3d_argmax_classes_dev(h3d_ctx* ctx, const double* d_value, int64_t n,
+                           int C, const uint8_t* d_member, uint8_t* d_cls);
+
+/* The clusters of h3d_label_components as lists (the arrays of
+ * thresholding.py:7-41 / classification.py:7-49's results): per cluster k of
+ * n_clusters its size[k] (int32), cls_of[k] = the class byte of its first
+ * member, and bounds (4, n_clusters) int32 = min row, max row, min col, max
+ * col. A cluster is kept when size >= max(min_size, 1); the kept clusters, in
+ * label order, are members[starts[j] .. starts[j + 1]) -- pixel indices in
+ * increasing order, so each cluster is in (row, col) order. All buffers are
+ * the caller's: members has room for n entries (*n_members are meaningful; the
+ * _dev form uses all n as sort space), starts for n_clusters + 1 (*n_kept + 1
+ * are written). A label outside [-1, n_clusters) is H3D_EARG. _dev: every
+ * array is a device pointer; n_kept and n_members are host words either way.
+ * Synchronous. */
+int h3d_cluster_lists(h3d_ctx* ctx, const int32_t* label, const uint8_t* cls,
+                      const int64_t* row, const int64_t* col, int64_t n,
+                      int64_t n_clusters, int64_t min_size, int32_t* size,
+                      uint8_t* cls_of, int32_t* bounds, int32_t* members,
+                      int64_t* starts, int64_t* n_kept, int64_t* n_members);
+int h3d_cluster_lists_dev(h3d_ctx* ctx, const int32_t* d_label,
+                          const uint8_t* d_cls, const int64_t* d_row,
+                          const int64_t* d_col, int64_t n, int64_t n_clusters,
+                          int64_t min_size, int32_t* d_size, uint8_t* d_cls_of,
+                          int32_t* d_bounds, int32_t* d_members,
+                          int64_t* d_starts, int64_t* n_kept,
+                          int64_t* n_members);
 
 /* ---- alternative models (analysis/alternatives.py) ---------------------- */
 

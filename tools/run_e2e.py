@@ -9,6 +9,11 @@ estimate_disp -> lrt -> bh, analysis.py:305-364 of the reference) and
 stages (write-behind) and the wait for the last of them is reported.
 
     python tools/run_e2e.py [--chroms 20] [--workers 16] [--keep DIR]
+                            [--collect-gpu]
+
+``--collect-gpu`` (single rank): afterwards collect() is run again from the
+q-values alone, default and with gpu=True, each with the seconds it spends in
+text formatting and file reads / writes (tools/calls_time.py collect_timed).
 
 Prints one JSON line. Under torchrun it runs the sharded path (each rank
 its LPT chromosomes, the distance re-shard, the sample-sort BH).
@@ -36,6 +41,8 @@ def main():
     ap.add_argument('--seed', type=int, default=3)
     ap.add_argument('--keep', default=None,
                     help='write the dataset and outdir here and keep them')
+    ap.add_argument('--collect-gpu', action='store_true',
+                    help='time collect() default and gpu=True side by side')
     ap.add_argument('--profile', type=int, default=0,
                     help='cProfile the stages, print the top N to stderr')
     args = ap.parse_args()
@@ -110,6 +117,12 @@ def main():
             'collect_s': collect_s, 'write_dataset_s': write_s,
             'loop_pixels_q_lt_0.05': int(np.sum(q < 0.05)),
         }
+        if args.collect_gpu and sh.world == 1:
+            sys.path.insert(0, os.path.join(REPO, 'tools'))
+            from calls_time import collect_timed
+            collect_timed(h, True)                  # grows the ctx's buffers
+            out['collect_default'] = collect_timed(h, False)
+            out['collect_gpu'] = collect_timed(h, True)
         if sh.rank == 0:
             print(json.dumps(out), flush=True)
     finally:
