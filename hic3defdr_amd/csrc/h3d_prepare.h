@@ -208,8 +208,17 @@ static __global__ void k_mor_keys(const double* __restrict__ balanced,
       lg[r] = log(v + 1);
     }
     const double gm = exp(np_sum<kMaxReps>(lg, R) / R) - 1;
-    for (int r = 0; r < R; ++r)
-      keys[(int64_t)r * n + k] = ok ? balanced[i * R + r] / gm : INFINITY;
+    // A valid row may hold +inf (a count over a zero bias): gm is inf and
+    // that replicate's ratio inf / inf = NaN, which np.median carries to the
+    // whole (bin, replicate). Such a key goes out as the NaN with the sign
+    // bit set, which the radix sort puts before every number (a NaN without
+    // it lands past the +inf of the invalid rows, outside the valid ones):
+    // k_mor_median finds it at the head of the segment.
+    for (int r = 0; r < R; ++r) {
+      double q = ok ? balanced[i * R + r] / gm : INFINITY;
+      if (q != q) q = __longlong_as_double((long long)0xFFF8000000000000ull);
+      keys[(int64_t)r * n + k] = q;
+    }
     // valid rows per bin: bins are sorted along k, so a wave spans one or
     // two bins -- one atomic per (wave, bin) instead of one per row
     const int b = bin[k];
@@ -236,7 +245,8 @@ static __global__ void k_mor_median(const double* __restrict__ sorted_keys,
   const int64_t base = (int64_t)r * n + bin_start[b];
   const int64_t m = valid[b];
   double med = NAN;
-  if (m > 0) {
+  // (a NaN among the valid ratios sorts to the head: np.median is NaN then)
+  if (m > 0 && sorted_keys[base] == sorted_keys[base]) {
     if (m % 2)
       med = sorted_keys[base + m / 2];
     else

@@ -587,9 +587,21 @@ int sf_bin_factors_scaling(SfCall& c) {
   if (int rc = d2h_sync(ctx, colsum.data(), c.d_spb, (size_t)nb * R * 8, s)) return rc;
   for (int b = 0; b < nb; ++b) {
     const double* cs = &colsum[(size_t)b * R];
+    // gmean is exp(nanmean(log(s + 1))) - 1: numpy's nanmean sums the logs
+    // with every NaN replaced by 0 and divides by the count of the others
+    // (0 / 0 = NaN when there is none), so a replicate whose column sum is
+    // NaN (a NaN-bias bin without a count: balanced 0 / NaN) gets a NaN
+    // factor and leaves the other replicates' factors finite
     double lg[kMaxReps];
-    for (int r = 0; r < R; ++r) lg[r] = std::log(cs[r] + 1);
-    const double gm = std::exp(np_sum<kMaxReps>(lg, R) / R) - 1;
+    int cnt = 0;
+    for (int r = 0; r < R; ++r) {
+      lg[r] = std::log(cs[r] + 1);
+      if (std::isnan(lg[r]))
+        lg[r] = 0.0;
+      else
+        ++cnt;
+    }
+    const double gm = std::exp(np_sum<kMaxReps>(lg, R) / cnt) - 1;
     for (int r = 0; r < R; ++r) c.spb[(size_t)b * R + r] = cs[r] / gm;
   }
   return 0;
