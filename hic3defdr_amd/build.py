@@ -6,7 +6,10 @@
 - ``libh3d_hosttest.so`` the device numerics compiled for the host, used only
                           by CPU unit tests (tests/test_special_host.py).
 - ``libh3d_selftest.so`` the same numerics compiled for gfx950 behind the same
-                          test ABI, used only by GPU unit tests.
+                          test ABI, used only by GPU unit tests. The entries
+                          the two share are one text, ``csrc/h3d_unit_abi.h``;
+                          ``h3d_hosttest.cpp`` (g++) and ``h3d_selftest.hip``
+                          (hipcc) put a serial loop or a kernel under it.
 - ``libh3d_peak.so``     bench.py's measured roofline denominators (an FP64
                           FMA-chain kernel and a 16 B/lane copy); measurement
                           only, never loaded by the product.

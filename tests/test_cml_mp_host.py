@@ -32,14 +32,13 @@ counts and nothing else; 1/1188 made 1/1189 (7e-14 at y = 10) stays inside
 the bound, which is 32 eps of |lgamma(10)| = 9e-14 per log-gamma there.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import cml_mp_cases as cc
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950, load_host
 
 D = ctypes.POINTER(ctypes.c_double)
 
@@ -47,19 +46,7 @@ D = ctypes.POINTER(ctypes.c_double)
 @pytest.fixture(scope='module',
                 params=['host', pytest.param('gfx950', marks=pytest.mark.gpu)])
 def lib(request):
-    if request.param == 'host':
-        return ctypes.CDLL(h3dbuild.build_hosttest())
-    # one HIP runtime per process, torch's first (test_special_host.py)
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-    if not os.path.exists(path):
-        raise RuntimeError('libh3d_selftest.so missing: run build()')
-    lib = ctypes.CDLL(path)
-    assert lib.h3dt_device_ok() == 1, 'no HIP device for the gfx950 self-test'
-    return lib
+    return load_host() if request.param == 'host' else load_gfx950()
 
 
 def terms(lib, ps, delta, mode):

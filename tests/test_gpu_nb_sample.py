@@ -12,13 +12,12 @@ self-test library (h3dt_sim_bm: the kernel's sim_bm on the device) against
 numpy in the reference's association, bit for bit; its counts then equal
 nb_sample fed those numpy means."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 from hic3defdr_amd import _native
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950
 
 pytestmark = pytest.mark.gpu
 
@@ -34,11 +33,7 @@ def ctx():
 
 @pytest.fixture(scope='module')
 def selftest(ctx):
-    path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-    if not os.path.exists(path):
-        raise RuntimeError('libh3d_selftest.so missing: run build()')
-    lib = ctypes.CDLL(path)
-    assert lib.h3dt_device_ok() == 1
+    lib = load_gfx950()
     lib.h3dt_nb_draw.restype = ctypes.c_int
     lib.h3dt_sim_bm.restype = ctypes.c_int
     return lib

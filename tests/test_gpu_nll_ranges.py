@@ -18,12 +18,11 @@ ranges (csrc/h3d_model.h), so every value must be bit-identical:
   (M = 4) instantiations; 2+2 takes the full ones.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950
 from test_gpu_nll_paths import _run, _same
 
 pytestmark = pytest.mark.gpu
@@ -40,16 +39,7 @@ _cache = {}
 
 def _lib():
     if 'lib' not in _cache:
-        try:  # one HIP runtime per process: torch's first
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-        if not os.path.exists(path):
-            raise RuntimeError('libh3d_selftest.so missing: run build()')
-        lib = ctypes.CDLL(path)
-        assert lib.h3dt_device_ok() == 1, 'no HIP device for the self-test'
-        _cache['lib'] = lib
+        _cache['lib'] = load_gfx950()
     return _cache['lib']
 
 

@@ -13,7 +13,6 @@ infinite values equal) -- no stored mean is limited by the reference's
 secant exit, so seed 21 stands.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -176,12 +175,8 @@ def test_launch_tails_give_the_same_bits(nb, fix, R):
 
 @pytest.fixture(scope='module')
 def selftest():
-    from hic3defdr_amd import build as h3dbuild
-    import torch  # noqa: F401  (one HIP runtime per process, torch's first)
-    path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-    lib = ctypes.CDLL(path)
-    assert lib.h3dt_device_ok() == 1
-    return lib
+    from unit_abi import load_gfx950
+    return load_gfx950()
 
 
 @pytest.mark.parametrize('R', R_LIST)

@@ -10,12 +10,11 @@ rounding of 1024 (m - 1/2) flips) with its two neighbours, every power of two
 of the double range (subnormals included), DBL_MIN / DBL_MAX and the
 subnormals next to them, and 10^5 seeded random doubles."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950, load_host
 
 D = ctypes.POINTER(ctypes.c_double)
 I = ctypes.POINTER(ctypes.c_int32)
@@ -72,22 +71,13 @@ def _unary(lib, name, x):
 
 def _host():
     if 'host' not in _cache:
-        _cache['host'] = ctypes.CDLL(h3dbuild.build_hosttest())
+        _cache['host'] = load_host()
     return _cache['host']
 
 
 def _device():
     if 'dev' not in _cache:
-        try:  # one HIP runtime per process: torch's first
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-        if not os.path.exists(path):
-            raise RuntimeError('libh3d_selftest.so missing: run build()')
-        lib = ctypes.CDLL(path)
-        assert lib.h3dt_device_ok() == 1, 'no HIP device for the self-test'
-        _cache['dev'] = lib
+        _cache['dev'] = load_gfx950()
     return _cache['dev']
 
 

@@ -15,7 +15,6 @@ test_special_host.py; (c) at most 1e-4 of a cell's draws may differ from
 scipy.stats.poisson.ppf, and those still meet (b); (d) a chi-square below
 chi2.isf(1e-6, df) and a mean within 5 standard errors."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -24,7 +23,7 @@ import scipy.stats as st
 
 from conftest import rel_err
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950, load_host
 
 D = ctypes.POINTER(ctypes.c_double)
 I = ctypes.POINTER(ctypes.c_int32)
@@ -39,18 +38,7 @@ H3D_FLAG_BADIN = 16
 @pytest.fixture(scope='module',
                 params=['host', pytest.param('gfx950', marks=pytest.mark.gpu)])
 def lib(request):
-    if request.param == 'host':
-        return ctypes.CDLL(h3dbuild.build_hosttest())
-    try:
-        import torch  # noqa: F401  (one HIP runtime per process: torch's)
-    except ImportError:
-        pass
-    path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-    if not os.path.exists(path):
-        raise RuntimeError('libh3d_selftest.so missing: run build()')
-    lib = ctypes.CDLL(path)
-    assert lib.h3dt_device_ok() == 1, 'no HIP device for the gfx950 self-test'
-    return lib
+    return load_host() if request.param == 'host' else load_gfx950()
 
 
 def nb_draw(lib, bm, disp, u1, u2):

@@ -9,13 +9,12 @@ largest values are 2^-53 and 1 - 2^-53 and 1 - u is exact. (With 53 bits the
 half would be a 54th: the largest value, 1 - 2^-54, is not a double and
 rounds to 1, outside the open interval the sampler needs.)"""
 import ctypes
-import os
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950, load_host
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
@@ -35,18 +34,7 @@ KNOWN = [
 @pytest.fixture(scope='module',
                 params=['host', pytest.param('gfx950', marks=pytest.mark.gpu)])
 def lib(request):
-    if request.param == 'host':
-        return ctypes.CDLL(h3dbuild.build_hosttest())
-    try:
-        import torch  # noqa: F401  (one HIP runtime per process: torch's)
-    except ImportError:
-        pass
-    path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-    if not os.path.exists(path):
-        raise RuntimeError('libh3d_selftest.so missing: run build()')
-    lib = ctypes.CDLL(path)
-    assert lib.h3dt_device_ok() == 1, 'no HIP device for the gfx950 self-test'
-    return lib
+    return load_host() if request.param == 'host' else load_gfx950()
 
 
 def philox_py(ctr, key):

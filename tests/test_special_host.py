@@ -10,7 +10,6 @@ test ABI (h3dt_*):
 
 Same tolerances for both."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -19,7 +18,7 @@ import scipy.special as sc
 import oracle
 from conftest import golden, rel_err
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950, load_host
 
 D = ctypes.POINTER(ctypes.c_double)
 I = ctypes.POINTER(ctypes.c_int32)
@@ -28,22 +27,7 @@ I = ctypes.POINTER(ctypes.c_int32)
 @pytest.fixture(scope='module',
                 params=['host', pytest.param('gfx950', marks=pytest.mark.gpu)])
 def lib(request):
-    if request.param == 'host':
-        return ctypes.CDLL(h3dbuild.build_hosttest())
-    # one HIP runtime per process: torch's first, as _native.load_library
-    # does (the selftest library loaded first leaves torch without devices
-    # for the GPU tests that run after this module)
-    try:
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    # prebuilt in-tree by build() (the GPU box does not compile)
-    path = os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so')
-    if not os.path.exists(path):
-        raise RuntimeError('libh3d_selftest.so missing: run build()')
-    lib = ctypes.CDLL(path)
-    assert lib.h3dt_device_ok() == 1, 'no HIP device for the gfx950 self-test'
-    return lib
+    return load_host() if request.param == 'host' else load_gfx950()
 
 
 def _p(a, t=D):

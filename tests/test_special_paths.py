@@ -21,7 +21,7 @@ import oracle
 from conftest import GOLDEN, golden, rel_err
 from test_special_host import D, I, _p, binary, igam_err, lib, unary  # noqa: F401
 
-from hic3defdr_amd import build as h3dbuild
+from unit_abi import load_gfx950, load_host
 
 LD = np.longdouble
 # the long-double references need the x87 format (64-bit significand)
@@ -99,10 +99,7 @@ def test_exp_fast_gfx950_equals_host_straight_line(mp_golden):
     """Every operation of exp_fast's gfx950 branch is a correctly rounded
     IEEE one, so the kernel returns the bits of the host's
     exp_fast_straight (gfx950 only: the host's exp_fast is libm's exp)."""
-    import torch  # noqa: F401  (one HIP runtime per process, torch's first)
-    dev = ctypes.CDLL(os.path.join(h3dbuild.LIBDIR, 'libh3d_selftest.so'))
-    assert dev.h3dt_device_ok() == 1
-    host = ctypes.CDLL(h3dbuild.build_hosttest())
+    dev, host = load_gfx950(), load_host()
     x = np.concatenate([exp_grids(), mp_golden['exp_x'], mp_golden['exp_edge_x']])
     got, want = unary(dev, 'exp_fast', x), unary(host, 'exp_fast_straight', x)
     diff = np.flatnonzero(bits(got) != bits(want))
