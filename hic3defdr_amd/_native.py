@@ -50,6 +50,7 @@ EXPORTS = [
     'h3d_label_components', 'h3d_label_components_dev',
     'h3d_threshold_classes_dev', 'h3d_argmax_classes_dev',
     'h3d_cluster_lists', 'h3d_cluster_lists_dev',
+    'h3d_cluster_stats', 'h3d_cluster_stats_dev',
 ]
 
 
@@ -80,6 +81,103 @@ CCL_MAX_CLASSES = 254
 CCL_MAX_N = 2 ** 31 - 2
 BAD_PIXELS = ('pixels must be distinct, in (row, col) order, with '
               'coordinates in [0, 2^31)')
+
+
+# per-cluster statistics (h3d_cluster_stats): the reducers as `want` bits, the
+# largest K, the flag bits of h3d.h
+CSTAT_WANT = {'mean': 1, 'max': 2, 'min': 4}
+CSTAT_MAX_K = 256
+CSTAT_REPEAT, CSTAT_ORDER, CSTAT_PIXEL, CSTAT_STARTS = 1, 2, 4, 8
+
+
+def cstat_want(reducers):
+    """The `want` bits of an iterable of reducer names (ValueError for a name
+    that is not 'mean', 'max' or 'min', or for none at all)."""
+    if isinstance(reducers, str):
+        reducers = (reducers,)
+    reducers = tuple(reducers)
+    for r in reducers:
+        if r not in CSTAT_WANT:
+            raise ValueError("reducer must be 'mean', 'max' or 'min', got %r"
+                             % (r,))
+    if not reducers:
+        raise ValueError('no reducer')
+    want = 0
+    for r in reducers:
+        want |= CSTAT_WANT[r]
+    return reducers, want
+
+
+def cstat_raise(flags):
+    """The exceptions of h3d_cluster_stats' flag bits."""
+    if flags & CSTAT_REPEAT:
+        raise ValueError('the table repeats a pixel, or has a coordinate '
+                         'outside [0, 2^31)')
+    if flags & CSTAT_ORDER:
+        raise ValueError('sorted=True, but the table is not in strictly '
+                         'increasing (row, col) order')
+    if flags & CSTAT_STARTS:
+        raise ValueError('starts must begin at 0 and every cluster must have '
+                         'a pixel')
+    if flags & CSTAT_PIXEL:
+        raise IndexError('a cluster pixel is outside the table\'s shape')
+
+
+def check_cluster_stats(row, col, data, prow, pcol, starts):
+    """The input rule of h3d_cluster_stats for host arrays, checked before a
+    device is touched. Table: integer ``row`` / ``col`` (n,) with coordinates
+    in [0, 2^31), n <= 2^31 - 2, ``data`` (n,) or (n, K) float, integer or
+    bool (converted to float64), 1 <= K <= 256. Clusters: integer ``prow`` /
+    ``pcol`` (p,), ``starts`` (k + 1,) from 0 to p, strictly increasing (an
+    empty cluster is a ValueError). A negative cluster coordinate is a
+    ValueError, one beyond the table's shape ``(max(row) + 1, max(col) + 1)``
+    an IndexError. Returns (row, col, data (n, K), prow, pcol, starts, n_rows,
+    n_cols) as contiguous int64 / float64."""
+    row, col, data = np.asarray(row), np.asarray(col), np.asarray(data)
+    prow, pcol, starts = np.asarray(prow), np.asarray(pcol), np.asarray(starts)
+    for a, what in ((row, 'row'), (col, 'col'), (prow, 'cluster rows'),
+                    (pcol, 'cluster columns'), (starts, 'starts')):
+        if a.dtype.kind not in 'iu' and a.size:
+            raise TypeError('%s must be integers, not %s' % (what, a.dtype))
+        if a.ndim != 1:
+            raise ValueError('%s must have 1 dimension' % what)
+    if data.dtype.kind not in 'fiub':
+        raise TypeError('data must be float, integer or bool, not %s'
+                        % data.dtype)
+    if data.ndim == 1:
+        data = data[:, None]
+    if data.ndim != 2:
+        raise ValueError('data must have 1 or 2 dimensions')
+    n = len(row)
+    if col.shape != row.shape or data.shape[0] != n:
+        raise ValueError('row, col and data must have one length')
+    if not 1 <= data.shape[1] <= CSTAT_MAX_K:
+        raise ValueError('between 1 and %d data columns, got %d'
+                         % (CSTAT_MAX_K, data.shape[1]))
+    if n > CCL_MAX_N or len(prow) > CCL_MAX_N:
+        raise ValueError('at most 2^31 - 2 pixels')
+    if pcol.shape != prow.shape:
+        raise ValueError('cluster rows and columns must have one length')
+    if len(starts) < 1 or starts[0] != 0 or starts[-1] != len(prow):
+        raise ValueError('starts must run from 0 to the number of cluster '
+                         'pixels')
+    if np.any(starts[1:] <= starts[:-1]):
+        raise ValueError('an empty cluster')
+    n_rows = n_cols = 0
+    if n:
+        if min(row.min(), col.min()) < 0 or \
+                max(row.max(), col.max()) >= 2 ** 31:
+            raise ValueError('row and col must be in [0, 2^31)')
+        n_rows, n_cols = int(row.max()) + 1, int(col.max()) + 1
+    if len(prow):
+        if min(prow.min(), pcol.min()) < 0:
+            raise ValueError('a cluster pixel has a negative coordinate')
+        if prow.max() >= n_rows or pcol.max() >= n_cols:
+            raise IndexError('a cluster pixel is outside the table\'s shape '
+                             '(%d, %d)' % (n_rows, n_cols))
+    return (_c(row, np.int64), _c(col, np.int64), _c(data, np.float64),
+            _c(prow, np.int64), _c(pcol, np.int64), _c(starts, np.int64),
+            n_rows, n_cols)
 
 
 def check_class_count(C):
@@ -255,6 +353,12 @@ def load_library(path=None):
                                        _P, _P, _P, _P, _P, _P, _P]),
             'h3d_cluster_lists_dev': (_I, [_P, _P, _P, _P, _P, _I64, _I64,
                                            _I64, _P, _P, _P, _P, _P, _P, _P]),
+            'h3d_cluster_stats': (_I, [_P, _P, _P, _P, _I64, _I, _I, _I64,
+                                       _I64, _P, _P, _P, _I64, _I, _P, _P, _P,
+                                       _P, _P]),
+            'h3d_cluster_stats_dev': (_I, [_P, _P, _P, _P, _I64, _I, _I, _I64,
+                                           _I64, _P, _P, _P, _I64, _I, _P, _P,
+                                           _P, _P, _P]),
         }
         for name, (res, args) in sig.items():
             if name in OPTIONAL and not hasattr(lib, name):
@@ -1281,6 +1385,85 @@ class Context(object):
             'h3d_cluster_lists_dev')
         return dict(size=size, cls_of=cls_of, bounds=bounds,
                     members=members[:nm.value], starts=starts[:nk.value + 1])
+
+    # -- per-cluster statistics (util/cluster_table.py) -----------------------
+    def cluster_stats(self, row, col, data, prow, pcol, starts,
+                      reducers=('mean',), sorted=False):
+        """dict reducer -> (k, K) float64, plus 'found' (k,) int32, of
+        h3d_cluster_stats on host arrays: the table ``row`` / ``col`` /
+        ``data`` (n, K) reduced over the pixels ``prow`` / ``pcol``
+        [starts[j], starts[j + 1]) of each of the k clusters; an absent pixel
+        counts as 0.0. ``sorted`` promises the table in strictly increasing
+        (row, col) order. The arguments are checked by
+        ``check_cluster_stats``; the library's flags become its exceptions
+        (a repeated table pixel or a broken promise: ValueError)."""
+        reducers, want = cstat_want(reducers)
+        row, col, data, prow, pcol, starts, n_rows, n_cols = \
+            check_cluster_stats(row, col, data, prow, pcol, starts)
+        k, K = len(starts) - 1, data.shape[1]
+        out = {r: np.empty((k, K), dtype=np.float64) for r in reducers}
+        found = np.zeros(k, dtype=np.int32)
+        fl = _I(0)
+        _check(self.lib.h3d_cluster_stats(
+            self.handle, _ptr(row), _ptr(col), _ptr(data), len(row), K,
+            int(bool(sorted)), n_rows, n_cols, _ptr(prow), _ptr(pcol),
+            _ptr(starts), k, want, _ptr(out.get('mean')),
+            _ptr(out.get('max')), _ptr(out.get('min')), _ptr(found),
+            ctypes.byref(fl)), 'h3d_cluster_stats')
+        cstat_raise(fl.value)
+        out['found'] = found
+        return out
+
+    def cluster_stats_dev(self, row, col, data, n_rows, n_cols, prow, pcol,
+                          starts, reducers=('mean',), sorted=False,
+                          check=True):
+        """cluster_stats on torch tensors of this ctx's device (row, col,
+        prow, pcol, starts int64; data (n, K) float64); ``n_rows`` /
+        ``n_cols`` bound the cluster pixels. Returns a dict of tensors.
+        ``check=False`` returns the library's flag word under 'flags'
+        instead of raising."""
+        import torch
+        reducers, want = cstat_want(reducers)
+        for t in (row, col, prow, pcol, starts):
+            if t.dtype != torch.int64 or t.dim() != 1:
+                raise ValueError('row, col, prow, pcol and starts must be '
+                                 'int64 with 1 dimension')
+        if data.dtype != torch.float64 or data.dim() != 2:
+            raise ValueError('data must be float64 (n, K)')
+        if col.shape != row.shape or data.shape[0] != row.shape[0] or \
+                pcol.shape != prow.shape or starts.numel() < 1:
+            raise ValueError('row, col, data (n,) and prow, pcol (p,)')
+        K = int(data.shape[1])
+        if not 1 <= K <= CSTAT_MAX_K:
+            raise ValueError('between 1 and %d data columns, got %d'
+                             % (CSTAT_MAX_K, K))
+        row, col, data = row.contiguous(), col.contiguous(), data.contiguous()
+        prow, pcol = prow.contiguous(), pcol.contiguous()
+        starts = starts.contiguous()
+        k, dev = starts.numel() - 1, row.device
+        # the library reads prow / pcol up to starts[k]
+        if k and int(starts[-1]) > prow.numel():
+            raise ValueError('starts ends beyond the cluster pixels')
+        out = {r: torch.empty((k, K), dtype=torch.float64, device=dev)
+               for r in reducers}
+        found = torch.zeros(k, dtype=torch.int32, device=dev)
+
+        def p(t):
+            return _P(t.data_ptr()) if t is not None else None
+        fl = _I(0)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self.lib.h3d_cluster_stats_dev(
+            self.handle, p(row), p(col), p(data), row.numel(), K,
+            int(bool(sorted)), int(n_rows), int(n_cols), p(prow), p(pcol),
+            p(starts), k, want, p(out.get('mean')), p(out.get('max')),
+            p(out.get('min')), p(found), ctypes.byref(fl)),
+            'h3d_cluster_stats_dev')
+        if check:
+            cstat_raise(fl.value)
+        else:
+            out['flags'] = fl.value
+        out['found'] = found
+        return out
 
     ROC_FIELDS = ('fdr', 'fpr', 'tpr', 'thresh', 'fps', 'tps')
 

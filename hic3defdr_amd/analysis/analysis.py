@@ -36,7 +36,8 @@ from hic3defdr_amd.analysis.resident import bias_stamps
 from hic3defdr_amd.util.classification import classify_clusters, \
     classify_clusters_gpu
 from hic3defdr_amd.util.cluster_table import ClusterTable
-from hic3defdr_amd.util.clusters import (load_cluster_list,
+from hic3defdr_amd.util.clusters import (cluster_text_pixels,
+                                         load_cluster_list,
                                          load_cluster_pixels,
                                          pixel_membership, save_clusters)
 from hic3defdr_amd.util.thresholding import threshold_clusters, \
@@ -713,3 +714,103 @@ class AnalyzingHiC3DeFDR(object):
                                       .with_classification(c))
                 ClusterTable.concat(tables).sorted().to_tsv(
                     '%s/results_%g_%i.tsv' % (self.outdir, f, s))
+
+    # stages whose columns are the replicates / the conditions (the other
+    # COO stages have one value per pixel)
+    _REP_STAGES = ('raw', 'size_factors', 'scaled')
+    _COND_STAGES = ('disp', 'mu_hat_alt')
+
+    def _annotation_names(self, stage, reducer):
+        if stage in self._REP_STAGES:
+            labels = list(self.design.index)
+        elif stage in self._COND_STAGES:
+            labels = list(self.design.columns)
+        else:
+            return ['%s_%s' % (stage, reducer)]
+        return ['%s_%s_%s' % (stage, label, reducer) for label in labels]
+
+    def annotate(self, fdr=0.05, cluster_size=3,
+                 columns=(('qvalues', 'min'), ('mu_hat_alt', 'mean')),
+                 outfile=None):
+        """``results_<fdr>_<size>.tsv`` with per-cluster statistics of outdir
+        stages -> ``results_<fdr>_<size>_annotated.tsv`` (or ``outfile``, for
+        one FDR and size). Not in the reference, which leaves it to
+        ``util.cluster_table.add_columns_to_cluster_table`` per column.
+
+        ``columns`` is a sequence of (stage, reducer): a stage
+        ``load_data(stage, chrom, coo=True)`` can load and 'mean', 'max' or
+        'min'. Each cluster's pixels are looked up in the stage's table (a
+        pixel the table lacks counts as 0) and reduced on the GPU
+        (h3d_cluster_stats); per chromosome a stage is loaded and uploaded
+        once for all its clusters and reducers. A one-value stage gives the
+        column ``<stage>_<reducer>``, a per-replicate stage
+        ``<stage>_<replicate>_<reducer>`` and a per-condition stage
+        ``<stage>_<condition>_<reducer>``, after the results file's own rows
+        and columns. Runs ``collect()`` first where the results file is
+        missing; writes no other file."""
+        columns = [tuple(c) for c in columns]
+        for c in columns:
+            if len(c) != 2:
+                raise ValueError('columns are (stage, reducer) pairs')
+            stage, reducer = c
+            if stage not in self._PIXEL_SET:
+                raise ValueError('stage %s cannot be loaded as COO' % (stage,))
+            _native.cstat_want(reducer)
+        fdrs = list(fdr) if hasattr(fdr, '__len__') else [fdr]
+        sizes = list(cluster_size) if hasattr(cluster_size, '__len__') \
+            else [cluster_size]
+        if outfile is not None and len(fdrs) * len(sizes) != 1:
+            raise ValueError('outfile names one table: pass one fdr and one '
+                             'cluster_size')
+        stages = {}
+        for stage, reducer in columns:
+            if reducer not in stages.setdefault(stage, []):
+                stages[stage].append(reducer)
+        for f in fdrs:
+            for s in sizes:
+                infile = '%s/results_%g_%i.tsv' % (self.outdir, f, s)
+                if not os.path.isfile(infile):
+                    self.collect(fdr=f, cluster_size=s)
+                table = ClusterTable.read_tsv(infile)
+                self._annotate_table(table, stages)
+                order = [n for c in columns
+                         for n in self._annotation_names(*c)]
+                table.extras = {n: table.extras[n]
+                                for n in dict.fromkeys(order)}
+                table.to_tsv(outfile or '%s/results_%g_%i_annotated.tsv'
+                             % (self.outdir, f, s))
+
+    def _annotate_table(self, table, stages):
+        """Fills ``table.extras`` with the columns of ``stages`` (stage ->
+        reducers), chromosome by chromosome."""
+        eprint('annotating differential interactions')
+        for stage, reducers in stages.items():
+            for r in reducers:
+                for name in self._annotation_names(stage, r):
+                    table.extras[name] = np.full(len(table), np.nan)
+        if not len(table):
+            return
+        prow, pcol, starts = cluster_text_pixels(table.cluster)
+        us, ds = np.array(table.us_chrom), np.array(table.ds_chrom)
+        ctx = self._ctx()
+        for ch in self.chroms:
+            rows = np.flatnonzero((us == ch) & (ds == ch))
+            if not len(rows):
+                continue
+            sz = starts[rows + 1] - starts[rows]
+            st = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum(sz, out=st[1:])
+            # the pixels of this chromosome's clusters, cluster by cluster
+            pix = np.repeat(starts[rows] - st[:-1], sz) + np.arange(st[-1])
+            for stage, reducers in stages.items():
+                row, col, data = self.load_data(stage, ch, coo=True)
+                out = ctx.cluster_stats(row, col, data, prow[pix], pcol[pix],
+                                        st, reducers=reducers, sorted=True)
+                for r in reducers:
+                    names = self._annotation_names(stage, r)
+                    if out[r].shape[1] != len(names):
+                        raise ValueError(
+                            'stage %s has %d columns, expected %d'
+                            % (stage, out[r].shape[1], len(names)))
+                    for i, name in enumerate(names):
+                        table.extras[name][rows] = out[r][:, i]

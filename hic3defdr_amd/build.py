@@ -4,7 +4,9 @@
                           (the units of ``NATIVE_SRCS`` below; links zlib),
                           loaded by hic3defdr_amd._native.
 - ``libh3d_hosttest.so`` the device numerics compiled for the host, used only
-                          by CPU unit tests (tests/test_special_host.py).
+                          by CPU unit tests (tests/test_special_host.py);
+                          ``h3d_hosttest_cstat.cpp`` adds the serial twin of
+                          ``h3d_cstat.hip``.
 - ``libh3d_selftest.so`` the same numerics compiled for gfx950 behind the same
                           test ABI, used only by GPU unit tests. The entries
                           the two share are one text, ``csrc/h3d_unit_abi.h``;
@@ -54,7 +56,8 @@ NATIVE_SRCS = [('h3d_api.hip', 'hipcc'), ('h3d_lrt.hip', 'hipcc'),
                ('h3d_views.hip', 'hipcc'), ('h3d_balance.hip', 'hipcc'),
                ('h3d_nb.hip', 'hipcc'), ('h3d_diag.hip', 'hipcc'),
                ('h3d_eval.hip', 'hipcc'), ('h3d_sim.hip', 'hipcc'),
-               ('h3d_clusters.hip', 'hipcc'), ('h3d_ctx.hip', 'hipcc'),
+               ('h3d_clusters.hip', 'hipcc'), ('h3d_cstat.hip', 'hipcc'),
+               ('h3d_ctx.hip', 'hipcc'),
                ('h3d_cub_sort_idx.hip', 'hipcc'), ('h3d_cub_sort_int.hip', 'hipcc'),
                ('h3d_cub_sort_f64.hip', 'hipcc'), ('h3d_cub_scan.hip', 'hipcc'),
                ('h3d_calls.cpp', 'g++'), ('h3d_npz.cpp', 'g++')]
@@ -112,10 +115,12 @@ def _headers():
 def build_hosttest(force=False):
     os.makedirs(LIBDIR, exist_ok=True)
     out = os.path.join(LIBDIR, 'libh3d_hosttest.so')
-    src = os.path.join(CSRC, 'h3d_hosttest.cpp')
+    # h3d_hosttest_cstat.cpp: the host twin of h3d_cstat.hip
+    srcs = [os.path.join(CSRC, s) for s in ('h3d_hosttest.cpp',
+                                            'h3d_hosttest_cstat.cpp')]
     cmd = ['g++', '-O2', '-std=c++17', '-shared', '-fPIC',
-           '-ffp-contract=off', '-o', out, src]
-    return _build(out, cmd, [src] + _headers(), force)
+           '-ffp-contract=off', '-o', out] + srcs
+    return _build(out, cmd, srcs + _headers(), force)
 
 
 def build_selftest(force=False):

@@ -251,6 +251,68 @@ def find_clusters_gpu(sig_points, connectivity=1):
                                 connectivity).to_sets()
 
 
+def cluster_pixels(clusters):
+    """(prow, pcol, starts) of ``clusters`` -- a ``ClusterList`` or a list of
+    pixel lists -- in list order, repeats kept."""
+    if isinstance(clusters, ClusterList):
+        prow, pcol = clusters.pixels()
+        return prow, pcol, clusters.starts
+    sizes = np.fromiter((len(c) for c in clusters), dtype=np.int64,
+                        count=len(clusters))
+    starts = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=starts[1:])
+    pix = np.array([p for c in clusters for p in c])
+    if pix.size == 0:
+        pix = np.zeros((0, 2), dtype=np.int64)
+    if pix.ndim != 2 or pix.shape[1] != 2:
+        raise ValueError('a cluster is a list of (row, col) pixels')
+    return pix[:, 0], pix[:, 1], starts
+
+
+def cluster_text_pixels(texts):
+    """(prow, pcol, starts) of the ``cluster`` cells of a cluster table
+    (``[[i, j], [i, j]]`` per row, the text ``ClusterTable.read_tsv`` keeps),
+    parsed by numpy's text reader over all rows at once."""
+    sizes = np.array([t.count('[') - 1 for t in texts], dtype=np.int64)
+    starts = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=starts[1:])
+    body = ' '.join(texts).encode('ascii').translate(_PIXEL_TEXT) \
+        .replace(b',', b' ').strip()
+    pix = np.fromstring(body.decode('ascii'), dtype=np.int64, sep=' ') \
+        if body else np.zeros(0, dtype=np.int64)
+    if len(pix) != 2 * starts[-1]:
+        raise ValueError('a cluster cell is not a list of [row, col] pairs')
+    pix = pix.reshape(-1, 2)
+    return pix[:, 0], pix[:, 1], starts
+
+
+def cluster_stats_gpu(clusters, row, col, data, reducers=('mean',), ctx=None,
+                      sorted=False):
+    """The sparse table ``(row, col, data)`` evaluated at the pixels of every
+    cluster and reduced per cluster (reference ``cluster_table.py:298-332``'s
+    arithmetic, h3d_cluster_stats): a pixel the table lacks counts as 0.0, a
+    pixel listed twice counts twice, 'mean' divides by the number of listed
+    pixels, 'max' / 'min' are NaN where a value is. ``clusters`` is a
+    ``ClusterList`` or a list of pixel lists; ``data`` is (n,) or (n, K).
+    Returns a dict from each of ``reducers`` to a (k, K) float64 array, plus
+    'found' (k,): how many of a cluster's pixels the table holds. The table
+    may come in any order (``sorted=True`` promises strictly increasing
+    (row, col) and saves the sort); a repeated table pixel, an empty cluster
+    or a negative cluster coordinate is a ValueError, a cluster pixel beyond
+    the table's shape an IndexError (DESIGN.md §2). There is no CPU fallback;
+    the arguments are checked before a device is touched."""
+    reducers, _ = _native.cstat_want(reducers)
+    prow, pcol, starts = cluster_pixels(clusters)
+    args = _native.check_cluster_stats(row, col, data, prow, pcol, starts)
+    if len(starts) == 1:
+        K = args[2].shape[1]
+        out = {r: np.zeros((0, K)) for r in reducers}
+        out['found'] = np.zeros(0, dtype=np.int32)
+        return out
+    ctx = ctx or _native.context()
+    return ctx.cluster_stats(*args[:6], reducers=reducers, sorted=sorted)
+
+
 def load_clusters(infile):
     """Reference ``clusters.py:176-193``: list of sets of (i, j) tuples."""
     with open(infile, 'r') as handle:

@@ -35,6 +35,9 @@
  *                              (threshold / classify with gpu=True)
  *   h3d_threshold_classes_dev <- util/thresholding.py:7-41 (q < fdr, q >= fdr)
  *   h3d_argmax_classes_dev <- util/classification.py:7-49 (np.argmax)
+ *   h3d_cluster_stats / _dev <- util/cluster_table.py:192-332
+ *                              add_columns_to_cluster_table (mean / max / min
+ *                              of a sparse table over every cluster's pixels)
  *   h3d_format_clusters    <- util/clusters.py:129-130 save_clusters text,
  *                              util/cluster_table.py:67 "cluster" column
  *   h3d_lrt_poisson        <- analysis/alternatives.py:17-42 poisson_lrt
@@ -599,6 +602,51 @@ int h3d_cluster_lists_dev(h3d_ctx* ctx, const int32_t* d_label,
                           int32_t* d_bounds, int32_t* d_members,
                           int64_t* d_starts, int64_t* n_kept,
                           int64_t* n_members);
+
+/* Per-cluster statistics of a sparse table (cluster_table.py:192-332
+ * add_columns_to_cluster_table's arithmetic). The table is n pixels (row[i],
+ * col[i]) int64 with coordinates in [0, 2^31), n <= 2^31 - 2, in any order,
+ * and data (n, K) float64 row-major, 1 <= K <= 256. sorted != 0 promises the
+ * outdir layout -- strictly increasing (row, col) -- which is verified on the
+ * device and saves the sort. Cluster k of n_clusters is the pixels prow / pcol
+ * [starts[k] .. starts[k + 1]) in list order (a pixel listed twice counts
+ * twice), starts[0] = 0, at most 2^31 - 2 pixels in all. A cluster pixel's
+ * value is the table's at its (row, col), or 0.0 where the table has no such
+ * pixel; per cluster and column the m values are reduced to mean (sum / m),
+ * max and min (a NaN among the m makes max and min NaN; every NaN is stored as
+ * 0x7ff8000000000000). want is a bit set of H3D_CSTAT_MEAN / _MAX / _MIN; each
+ * wanted output is (n_clusters, K) float64, the others may be NULL. found
+ * (n_clusters) int32, may be NULL: how many of the cluster's pixels the table
+ * holds. Bad input sets bits in *flags beside rc 0, and the outputs are then
+ * unspecified: H3D_CSTAT_REPEAT a table pixel twice or outside [0, 2^31),
+ * H3D_CSTAT_ORDER a broken `sorted` promise, H3D_CSTAT_PIXEL a cluster pixel
+ * outside [0, n_rows) x [0, n_cols), H3D_CSTAT_STARTS starts[0] != 0 or a
+ * cluster without pixels. n_clusters = 0 launches nothing; n = 0 is legal
+ * (every value 0). The sums are stored and folded in a fixed order (no
+ * floating-point atomics): a cluster's results depend on its own pixel list,
+ * the table and K alone, and repeat bit for bit. _dev: every array is a
+ * device pointer; flags is a host word either way. Synchronous. */
+#define H3D_CSTAT_MEAN 1
+#define H3D_CSTAT_MAX 2
+#define H3D_CSTAT_MIN 4
+#define H3D_CSTAT_REPEAT 1
+#define H3D_CSTAT_ORDER 2
+#define H3D_CSTAT_PIXEL 4
+#define H3D_CSTAT_STARTS 8
+int h3d_cluster_stats(h3d_ctx* ctx, const int64_t* row, const int64_t* col,
+                      const double* data, int64_t n, int K, int sorted,
+                      int64_t n_rows, int64_t n_cols, const int64_t* prow,
+                      const int64_t* pcol, const int64_t* starts,
+                      int64_t n_clusters, int want, double* mean, double* vmax,
+                      double* vmin, int32_t* found, int* flags);
+int h3d_cluster_stats_dev(h3d_ctx* ctx, const int64_t* d_row,
+                          const int64_t* d_col, const double* d_data,
+                          int64_t n, int K, int sorted, int64_t n_rows,
+                          int64_t n_cols, const int64_t* d_prow,
+                          const int64_t* d_pcol, const int64_t* d_starts,
+                          int64_t n_clusters, int want, double* d_mean,
+                          double* d_max, double* d_min, int32_t* d_found,
+                          int* flags);
 
 /* ---- alternative models (analysis/alternatives.py) ---------------------- */
 
